@@ -5,8 +5,15 @@ per GPU, fp32, world pose of gripper_link (3x4) + 6x8 geometric Jacobian
 (with_rot=true, rpy_jac=false, no base).  One step = one launch of the engine
 over the whole batch; inputs are resident in HBM before timing starts.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1048576]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--n 1048576] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps of the headline and prints the result line.
+`--full` adds every other leg (roofline ceilings, cold-cache and large-batch checks, the other layouts
+and precisions, configs 2 / 4 / 5, the collision-aware IK legs, the strong-scaling leg of a group run,
+the CPU baseline; `--extras 0` / `--no-cpu` switch parts of it off).  `--dump-outputs DIR` writes what
+the last timed step of the headline computed -- the gripper pose and the Jacobian of a fixed, seeded
+sample of the batch's configurations -- as DIR/pose.npy and DIR/jacobian.npy (float32).
 
 Multi-GPU: configurations are independent, each rank evaluates its own 2^20
 slice of one global counter-hashed dataset (weak scaling, no collective in the
@@ -729,14 +736,43 @@ def _cold_leg(leg, n, stream, bytes_per_eval, reps=10, tiled=True):
             "method": "each launch after a 1 GiB read of another buffer (Infinity Cache evicted), 10 launches"}
 
 
+DUMP_SAMPLE = 65536  # configurations of --dump-outputs: 60 fp32 values each, 15.7 MB in all
+
+
+def _dump_outputs(path, poses, jac, n, tiled, rank, ws):
+    """--dump-outputs: the headline's output buffers after its last timed step, as a caller reads them --
+    pose.npy (links, 12, S) and jacobian.npy (8, 6, S), float32, for S = min(n, DUMP_SAMPLE) configurations of
+    this rank's batch: a fixed, seeded draw of column indices, ascending (all of them when n <= DUMP_SAMPLE).
+    A group run writes one pair per rank (pose_rank<r>.npy)."""
+    idx = np.arange(n)
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(20261015).choice(n, DUMP_SAMPLE, replace=False))
+    idx = torch.from_numpy(idx).to(poses.device)
+    os.makedirs(path, exist_ok=True)
+    for name, X in (("pose", poses), ("jacobian", jac)):
+        if tiled:  # (ntiles, ..., tile): configuration c is lane c % tile of tile c // tile
+            tile = X.shape[-1]
+            S = X[idx // tile, ..., idx % tile].movedim(0, -1)
+        else:
+            S = X[..., idx]
+        suffix = f"_rank{rank}" if ws > 1 else ""
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), S.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--n", type=int, default=1 << 20, help="configurations per GPU")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--extras", type=int, default=1, help="also time fp64 FK+J, config 2, IK and collision legs")
+    ap.add_argument("--full", action="store_true",
+                    help="every leg beside the headline: roofline ceilings, other layouts / precisions / configs, "
+                         "the strong-scaling leg of a group run, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline's outputs of its last timed step (a fixed sample) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--extras", type=int, default=1,
+                    help="with --full: also time fp64 FK+J, config 2, IK and collision legs (0: only the CPU baseline)")
     ap.add_argument("--row-pad", type=int, default=256, help="elements of padding per SoA row (ld = n + pad)")
     ap.add_argument("--layout", choices=["tiled", "soa"], default="tiled",
                     help="headline layout: tiled SoA (kin_plan_run_tiled) or plain SoA rows (kin_plan_run)")
@@ -746,6 +782,8 @@ def main():
                     help="1: plan-specialised kernels (kin_plan_specialize), 0: the generic kernels")
     ap.add_argument("--sweep", action="store_true", help="batch-size sweep, unpadded rows, strong scaling")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.extras = 0
 
     # stdout carries the one JSON line only: RCCL prints its version banner to the process's stdout when the
     # group initialises (a round-6 one-rank RCCL run had four such lines before the JSON), so until the line is
@@ -795,10 +833,11 @@ def main():
         J = torch.zeros((nt, 8, 6, tile), dtype=dtype, device=dev) if jac else None
         return plan, Qt, poses, J
 
-    def timed_leg(dtype, jac, links, layout, n=N, start=None, steps=args.steps, warmup=args.warmup):
+    def timed_leg(dtype, jac, links, layout, n=N, start=None, steps=args.steps, warmup=args.warmup, keep=None):
         """(wall s, device s) of `steps` launches of one FK(+J) workload in `layout`:
         "tiled" / "tileT" (kin_plan_run_tiled) or "soa" / "soa_padP" (kin_plan_run); a "generic_"
-        prefix runs the generic (not plan-specialised) kernel."""
+        prefix runs the generic (not plan-specialised) kernel.  `keep`: a list that receives the leg's
+        output buffers (poses, jacobian) as the last launch left them."""
         spec = args.spec
         if layout.startswith("generic_"):
             spec, layout = 0, layout[8:]
@@ -810,11 +849,17 @@ def main():
             pad = args.row_pad if layout == "soa" else int(layout[7:])
             plan, Qx, Px, Jx = leg(dtype, jac, links, n=n, pad=pad, start=start, spec=spec)
             r = _time_plan(plan, Qx, Px, Jx, steps, warmup, ctx, stream)
+        if keep is not None:
+            keep.extend((Px, Jx))
         del plan, Qx, Px, Jx
         return r
 
     # ---- headline: FK + J, fp32 -------------------------------------------------
-    wall, dev_s = timed_leg(torch.float32, True, [gl], args.layout)
+    kept = [] if args.dump_outputs else None
+    wall, dev_s = timed_leg(torch.float32, True, [gl], args.layout, keep=kept)
+    if kept:
+        _dump_outputs(args.dump_outputs, kept[0], kept[1], N, args.layout == "tiled", rank, ws)
+        del kept[:]
     headline_spec = bool(args.spec) and not SPEC_ERRORS
     evals = N * ws * args.steps
     value = evals / wall
@@ -920,7 +965,7 @@ def main():
                 sweep[f"2^{lg} {name}"] = {"evals_per_s": n_s * ws * k_s / ws_, "avg_launch_us": ds_ / k_s * 1e6,
                                            "achieved_GBs": bytes_per_eval * n_s / (ds_ / k_s) / 1e9}
         out["batch_sweep_fk_jac_f32"] = sweep
-    if ctx.dist is not None:  # strong scaling: one global 2^20 batch split across the ranks
+    if args.full and ctx.dist is not None:  # strong scaling: one global 2^20 batch split across the ranks
         st0, cnt = D.split_range(N, rank, ws)
         w_s, d_s = timed_leg(torch.float32, True, [gl], args.layout, n=cnt, start=st0)
         out["strong_scaling_fk_jac_f32"] = {"global_batch": N, "value": N * args.steps / w_s, "unit": "evals/s",
@@ -972,7 +1017,7 @@ def main():
                 "a11_nakamura_f64": _nakamura_leg(m, arm, gl, ctx, stream, spec=0)["value"]}
     if SPEC_ERRORS:
         out["specialization_errors"] = SPEC_ERRORS
-    if rank == 0 and ws == 1 and not args.no_cpu:  # the CPU baseline is a single-GPU-run figure
+    if args.full and rank == 0 and ws == 1 and not args.no_cpu:  # the CPU baseline is a single-GPU-run figure
         out["cpu_baseline"] = _cpu_baseline(m)
     sys.stdout.flush()
     os.dup2(json_fd, 1)

@@ -1,17 +1,19 @@
 #!/bin/bash
 # The one GPU-box session driver (replaces the per-round r0N_*.sh scripts).  Every GPU step runs under
-# its own time limit and the script stops at the first failure; output goes under gpurun_out/.
-#   gpurun -- bash tools/gpu_session.sh <step> [<step> ...]
+# its own time limit and the script stops at the first failure; output goes under $OUT/ (the directory
+# KINHIP_SESSION_OUT names, relative to the repository root; default session_out/).
+#   bash tools/gpu_session.sh <step> [<step> ...]
 # steps:
 #   tests[=<pytest selection>]  the GPU suite (default: tests/), -x, per-test timeout
 #   alltests=<pytest selection> the same without -x (every failure of a new batch of tests in one call)
 #   isa                         the bench on the A/B build with KINHIP_JIT_CODE_DUMP (every specialised code object
 #                               the bench compiles) + tools/isa_check.py over them and the generic kernels
 #   smoke                       __graft_entry__.smoke()
-#   bench                       python bench.py -> gpurun_out/bench.json
-#   bench-driver                the driver's command (--gpus 1 --steps 20 --warmup 5) -> gpurun_out/bench_driver.json
-#   bench-trace                 rocprofv3 --kernel-trace --stats of `bench.py --no-cpu` (gpurun_out/prof/bench)
-#   sweep                       python bench.py --no-cpu --sweep -> gpurun_out/bench_sweep.json
+#   bench                       python bench.py --full (every leg) -> $OUT/bench.json
+#   bench-driver                the driver's plain command (--gpus 1 --steps 20 --warmup 5: the headline alone)
+#                               -> $OUT/bench_driver.json
+#   bench-trace                 rocprofv3 --kernel-trace --stats of `bench.py --full --no-cpu` ($OUT/prof/bench)
+#   sweep                       python bench.py --full --no-cpu --sweep -> $OUT/bench_sweep.json
 #   rccl                        the RCCL test + the bench under a one-rank RCCL group (KINHIP_DIST_ALWAYS_GROUP=1)
 #   pmc=<tag>:<workload>[,...]  per workload a kernel trace + stats, then separate --pmc passes (never with
 #                               trace domains; each pass within the per-block counter limits); workloads of
@@ -38,16 +40,17 @@
 #                               alternated <reps> times; any KINHIP_JIT_SRC_DIR in the caller's environment also
 #                               applies to the other steps (e.g. ikt-sections)
 set -u -o pipefail
-mkdir -p gpurun_out/prof
+OUT=${KINHIP_SESSION_OUT:-session_out}
+mkdir -p $OUT/prof
 export TMPDIR=/tmp
 AB=$PWD/kinematics.jl_amd/lib/libkinhip_ab.so
 quiet() { grep -v "amdgpu.ids" || true; }
 
 pmc_run() {  # pmc_run <dir> <workload args> <rocprofv3 args...>
   local d=$1 w=$2; shift 2
-  timeout -k 10 240 rocprofv3 "$@" --output-format csv -d gpurun_out/prof/$d -o $d -- python3 tools/prof_kernel.py $w \
-    > gpurun_out/prof_$d.log 2>&1
-  local rc=$?; echo "$d rc=$rc"; [ $rc -eq 0 ] || { tail -5 gpurun_out/prof_$d.log; exit $rc; }
+  timeout -k 10 240 rocprofv3 "$@" --output-format csv -d $OUT/prof/$d -o $d -- python3 tools/prof_kernel.py $w \
+    > $OUT/prof_$d.log 2>&1
+  local rc=$?; echo "$d rc=$rc"; [ $rc -eq 0 ] || { tail -5 $OUT/prof_$d.log; exit $rc; }
 }
 
 for step in "$@"; do
@@ -56,29 +59,29 @@ for step in "$@"; do
     tests|tests=*)
       sel=${step#tests}; sel=${sel#=}; sel=${sel:-tests}
       timeout -k 10 1500 python -u -m pytest $sel -m gpu -x -v --timeout 300 --timeout-method thread \
-        > gpurun_out/gpu_tests.log 2>&1
-      rc=$?; tail -3 gpurun_out/gpu_tests.log
-      [ $rc -eq 0 ] || { grep -E "FAILED|Error" gpurun_out/gpu_tests.log | head -30; exit $rc; } ;;
+        > $OUT/gpu_tests.log 2>&1
+      rc=$?; tail -3 $OUT/gpu_tests.log
+      [ $rc -eq 0 ] || { grep -E "FAILED|Error" $OUT/gpu_tests.log | head -30; exit $rc; } ;;
     alltests=*)
       sel=${step#alltests=}
       timeout -k 10 1500 python -u -m pytest $sel -m gpu -v --timeout 300 --timeout-method thread \
-        > gpurun_out/gpu_tests_all.log 2>&1
-      rc=$?; tail -3 gpurun_out/gpu_tests_all.log
-      [ $rc -eq 0 ] || grep -E "FAILED|Error" gpurun_out/gpu_tests_all.log | head -30 ;;
+        > $OUT/gpu_tests_all.log 2>&1
+      rc=$?; tail -3 $OUT/gpu_tests_all.log
+      [ $rc -eq 0 ] || grep -E "FAILED|Error" $OUT/gpu_tests_all.log | head -30 ;;
     isa)
-      mkdir -p gpurun_out/isa
-      timeout -k 10 400 env KINHIP_LIB=$AB KINHIP_JIT_CODE_DUMP=$PWD/gpurun_out/isa/jit KINHIP_JIT_DUMP=$PWD/gpurun_out/isa/src \
-        python bench.py --no-cpu > gpurun_out/isa/bench_ab.json 2> gpurun_out/isa/bench_ab.err || { tail gpurun_out/isa/bench_ab.err; exit 9; }
-      python tools/isa_check.py gpurun_out/isa/jit.*.co > gpurun_out/isa/isa_check.txt 2>&1; tail -3 gpurun_out/isa/isa_check.txt ;;
+      mkdir -p $OUT/isa
+      timeout -k 10 400 env KINHIP_LIB=$AB KINHIP_JIT_CODE_DUMP=$PWD/$OUT/isa/jit KINHIP_JIT_DUMP=$PWD/$OUT/isa/src \
+        python bench.py --full --no-cpu > $OUT/isa/bench_ab.json 2> $OUT/isa/bench_ab.err || { tail $OUT/isa/bench_ab.err; exit 9; }
+      python tools/isa_check.py $OUT/isa/jit.*.co > $OUT/isa/isa_check.txt 2>&1; tail -3 $OUT/isa/isa_check.txt ;;
     pr2-alt)
-      timeout -k 10 600 python tools/pr2_alt_probe.py > gpurun_out/pr2_alt_probe.json 2> gpurun_out/pr2_alt_probe.err \
-        || { tail -20 gpurun_out/pr2_alt_probe.err; exit 12; }
-      cat gpurun_out/pr2_alt_probe.json ;;
+      timeout -k 10 600 python tools/pr2_alt_probe.py > $OUT/pr2_alt_probe.json 2> $OUT/pr2_alt_probe.err \
+        || { tail -20 $OUT/pr2_alt_probe.err; exit 12; }
+      cat $OUT/pr2_alt_probe.json ;;
     pr2-miss|pr2-miss=*)
       n=${step#pr2-miss}; n=${n#=}; n=${n:-200}
-      timeout -k 10 900 python tools/pr2_miss_study.py $n > gpurun_out/pr2_miss_study.json 2> gpurun_out/pr2_miss_study.err \
-        || { tail -20 gpurun_out/pr2_miss_study.err; exit 11; }
-      cut -c1-1500 gpurun_out/pr2_miss_study.json ;;
+      timeout -k 10 900 python tools/pr2_miss_study.py $n > $OUT/pr2_miss_study.json 2> $OUT/pr2_miss_study.err \
+        || { tail -20 $OUT/pr2_miss_study.err; exit 11; }
+      cut -c1-1500 $OUT/pr2_miss_study.json ;;
     scene-const)
       for r in 1 2 3; do
         for c in 0 1; do
@@ -87,34 +90,34 @@ for step in "$@"; do
       done
       for c in 0 1; do
         timeout -k 10 180 env SCENE_AB_CONST=$c rocprofv3 --kernel-trace --stats --output-format csv \
-          -d gpurun_out/prof/scene$c -o scene$c -- python3 tools/scene_ab.py 3 > gpurun_out/prof_scene$c.log 2>&1 \
-          || { tail -5 gpurun_out/prof_scene$c.log; exit 12; }
+          -d $OUT/prof/scene$c -o scene$c -- python3 tools/scene_ab.py 3 > $OUT/prof_scene$c.log 2>&1 \
+          || { tail -5 $OUT/prof_scene$c.log; exit 12; }
       done ;;
     pts-probe)
-      timeout -k 10 60 tools/pts_probe > gpurun_out/pts_probe.txt 2>&1; rc=$?; cat gpurun_out/pts_probe.txt
+      timeout -k 10 60 tools/pts_probe > $OUT/pts_probe.txt 2>&1; rc=$?; cat $OUT/pts_probe.txt
       [ $rc -eq 0 ] || exit 10 ;;
     smoke)
       timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | quiet || exit 2 ;;
     bench)
-      timeout -k 10 400 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail gpurun_out/bench.err; exit 3; }
-      cut -c1-400 gpurun_out/bench.json ;;
+      timeout -k 10 400 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 3; }
+      cut -c1-400 $OUT/bench.json ;;
     bench-driver)
-      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/bench_driver.json \
-        2> gpurun_out/bench_driver.err || { tail gpurun_out/bench_driver.err; exit 3; }
-      cut -c1-300 gpurun_out/bench_driver.json ;;
+      timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json \
+        2> $OUT/bench_driver.err || { tail $OUT/bench_driver.err; exit 3; }
+      cut -c1-300 $OUT/bench_driver.json ;;
     bench-trace)
-      timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/bench -o bench -- \
-        python3 bench.py --no-cpu > gpurun_out/bench_rocprof.log 2>&1 || { tail gpurun_out/bench_rocprof.log; exit 4; } ;;
+      timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof/bench -o bench -- \
+        python3 bench.py --full --no-cpu > $OUT/bench_rocprof.log 2>&1 || { tail $OUT/bench_rocprof.log; exit 4; } ;;
     sweep)
-      timeout -k 10 600 python bench.py --no-cpu --sweep --steps 20 > gpurun_out/bench_sweep.json \
-        2> gpurun_out/bench_sweep.err || { tail gpurun_out/bench_sweep.err; exit 5; } ;;
+      timeout -k 10 600 python bench.py --full --no-cpu --sweep --steps 20 > $OUT/bench_sweep.json \
+        2> $OUT/bench_sweep.err || { tail $OUT/bench_sweep.err; exit 5; } ;;
     rccl)
       timeout -k 10 240 python -u -m pytest tests/test_dist_gpu.py -m gpu -x -v --timeout 200 --timeout-method thread \
-        > gpurun_out/rccl_tests.log 2>&1 || { tail -20 gpurun_out/rccl_tests.log; exit 6; }
-      tail -2 gpurun_out/rccl_tests.log
+        > $OUT/rccl_tests.log 2>&1 || { tail -20 $OUT/rccl_tests.log; exit 6; }
+      tail -2 $OUT/rccl_tests.log
       timeout -k 10 400 env KINHIP_DIST_ALWAYS_GROUP=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 \
-        --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --no-cpu > gpurun_out/bench_rccl_1rank.json \
-        2> gpurun_out/bench_rccl_1rank.err || { tail gpurun_out/bench_rccl_1rank.err; exit 6; } ;;
+        --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --full --no-cpu > $OUT/bench_rccl_1rank.json \
+        2> $OUT/bench_rccl_1rank.err || { tail $OUT/bench_rccl_1rank.err; exit 6; } ;;
     pmc=*)
       IFS=, read -ra specs <<< "${step#pmc=}"
       for spec in "${specs[@]}"; do
@@ -148,24 +151,24 @@ for step in "$@"; do
     ik-timeline)
       timeout -k 10 120 env KINHIP_LIB=$AB KINHIP_JIT_DEFS=-DKINHIP_IK_SECT=9 python -u tools/ik_timeline.py 2>&1 | quiet || exit 8 ;;
     ik-dump)
-      mkdir -p gpurun_out/jit gpurun_out/ikprof
-      timeout -k 10 120 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/gpurun_out/jit/ik AB_SPEC=1 AB_F32=1 IK_N=65536 \
+      mkdir -p $OUT/jit $OUT/ikprof
+      timeout -k 10 120 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/$OUT/jit/ik AB_SPEC=1 AB_F32=1 IK_N=65536 \
         python -u tools/ik_ab.py 2>&1 | quiet || exit 8
-      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d gpurun_out/ikprof -o ik -- python3 -u tools/ik_ab.py \
-        > gpurun_out/ikprof/run.log 2>&1 || exit 7 ;;
+      timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/ikprof -o ik -- python3 -u tools/ik_ab.py \
+        > $OUT/ikprof/run.log 2>&1 || exit 7 ;;
     dumps)  # the specialised IK sources (both precisions) and the collision-IK ones, for offline ISA work
-      mkdir -p gpurun_out/jit
-      timeout -k 10 200 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/gpurun_out/jit/ik AB_SPEC=1 IK_N=65536 \
+      mkdir -p $OUT/jit
+      timeout -k 10 200 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/$OUT/jit/ik AB_SPEC=1 IK_N=65536 \
         python -u tools/ik_ab.py 2>&1 | quiet || exit 8
-      timeout -k 10 300 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/gpurun_out/jit/cik AB_SPEC=1 \
+      timeout -k 10 300 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/$OUT/jit/cik AB_SPEC=1 \
         python -u tools/cik_ab.py 2>&1 | quiet || exit 8 ;;
     coll)
       timeout -k 10 200 python -u tools/coll_pad_ab.py 2>&1 | quiet || exit 8 ;;
     cik)
       timeout -k 10 200 python -u tools/cik_bench.py 2>&1 | quiet || exit 8 ;;
     coll-dump)
-      mkdir -p gpurun_out/jit
-      timeout -k 10 200 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/gpurun_out/jit/coll AB_SPEC=1 \
+      mkdir -p $OUT/jit
+      timeout -k 10 200 env KINHIP_LIB=$AB KINHIP_JIT_DUMP=$PWD/$OUT/jit/coll AB_SPEC=1 \
         python -u tools/coll_spec_ab.py 2>&1 | quiet || exit 8 ;;
     srcab=*)  # srcab=<tool.py>:<reps>: the A/B build with the JIT device headers of gpurun_ab/old vs csrc/, alternated
       spec=${step#srcab=}; tool=${spec%%:*}; reps=${spec#*:}

@@ -1,4 +1,5 @@
-"""Summarise rocprofv3 outputs under gpurun_out/prof into committed profiles/ files.
+"""Summarise rocprofv3 outputs of tools/gpu_session.sh (its output directory's prof/: KINHIP_SESSION_OUT,
+default session_out/) into committed profiles/ files.
 
 HBM bytes per launch follow MI355X_MICROARCH.md (HBM / rocprofv3 section):
 FETCH_SIZE and WRITE_SIZE are in KB; on gfx950 FETCH_SIZE reports half of the
@@ -15,7 +16,7 @@ import os
 import shutil
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PROF = os.path.join(ROOT, "gpurun_out", "prof")
+PROF = os.path.join(ROOT, os.environ.get("KINHIP_SESSION_OUT", "session_out"), "prof")
 OUT = os.path.join(ROOT, "profiles")
 
 WORK = {  # workload -> (kernel substring, algorithmic bytes per launch, note)
