@@ -379,7 +379,7 @@ def ik_coll_batch(mech: "OracleMech", sdf: "OracleUnionSDF", q0, q_joint_ids, li
 
 
 def ikc_sphere_order(tree: UrdfTree, q_joint_ids, link_id, sphere_links):
-    """The order in which kin_ik_coll_batch adds the sphere rows (kinhip_host.cpp stage_ikc_tree): spheres on
+    """The order in which kin_ik_coll_batch adds the sphere rows (kinhip_stage.cpp stage_ikc_tree): spheres on
     the root frame first, then by the depth-first position (children in joint order) of the moving joint
     whose frame carries them, the caller's order inside a carrier."""
     J = len(tree.joint_names)

@@ -1,6 +1,6 @@
 // Host sanitizer harness (test infrastructure; tests/test_host_sanitizers.py): drives the engine's
-// host code -- the URDF reader (kinhip_urdf.cpp), tree validation, rptable, add_link and plan staging
-// (kinhip_host.cpp) -- under ASan + UBSan, on the given URDF files and on seeded corruptions of them.
+// host code -- the URDF reader (kinhip_urdf.cpp), tree validation, rptable, add_link (kinhip_model.cpp) and plan
+// staging (kinhip_stage.cpp) -- under ASan + UBSan, on the given URDF files and on seeded corruptions of them.
 //   kin_host_harness [--mutants K] [--seed S] file.urdf ...
 // Exit 0 when every call returned a kin_status (no crash, no sanitizer report); prints a summary.
 #include <cstdint>

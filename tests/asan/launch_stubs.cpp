@@ -1,6 +1,6 @@
-// Test-only: the host sanitizer harness links the engine's host translation units (kinhip_host.cpp,
-// kinhip_urdf.cpp, kinhip_jit.cpp) without the gfx950 kernel TUs; these launchers stand in for them and
-// report "no device" (a plan never reaches them in a sanitizer run: staging needs a device first).
+// Test-only: the host sanitizer harness links the engine's host translation units (SRCS_CPP of
+// kinematics.jl_amd/csrc/Makefile) without the gfx950 kernel TUs; these launchers stand in for them and
+// report "no device" (a plan never reaches them in a sanitizer run: plan creation needs a device first).
 #include "kinhip_internal.h"
 
 namespace kinhip {

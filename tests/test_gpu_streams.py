@@ -2,7 +2,7 @@
 names each calling thread's own default stream, so the two-phase IK's scratch sets (hand-over rings, fail
 lists) may be taken by calls on different streams.  Since round 6 every call that takes a set is ordered
 after the set's previous call (stream order on the same stream, else a host wait on the set's event while
-that call is in flight; kinhip_host.cpp), so any number of threads, streams or handles share the 4 sets
+that call is in flight; kinhip_ik_sets.h), so any number of threads, streams or handles share the 4 sets
 without ever running two calls in one set.
 
 Every result must equal the single-threaded reference bit for bit, however the main thread reads them.
@@ -104,7 +104,7 @@ def _run(config4, n_threads, streams, reps=6, sync="stream", concurrent=True):
         for t, ev in enumerate(events):
             rc = hip.hipEventSynchronize(ev)
             if rc == HIP_ERROR_CAPTURED_EVENT and streams[t] == HIP_STREAM_PER_THREAD and not th[t].is_alive():
-                # the runtime defect the library guards against (kinhip_host.cpp ik_set_state): an event recorded
+                # the runtime defect the library guards against (kinhip_ik_sets.h set_state): an event recorded
                 # on the per-thread stream of a thread that has exited may report hipErrorCapturedEvent
                 # (profiles/r06_gpu_tests_capturedevent.log); that exit drained the stream, so the read is complete
                 hip.hipGetLastError()
