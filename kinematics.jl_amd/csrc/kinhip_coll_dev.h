@@ -42,11 +42,9 @@ __device__ __forceinline__ double signed_sqrt(double k) { return copysign(sqrt(f
 #if KINHIP_COLL_SOFF
 #define KIN_CO_LD ldo_soa
 #define KIN_CO_ST sto_soa
-#define KIN_CO_ST2 sto_soa2
 #else
 #define KIN_CO_LD ld_soa
 #define KIN_CO_ST st_soa
-#define KIN_CO_ST2 st_soa2
 #endif
 
 #ifndef KINHIP_AABB_UNROLL
@@ -192,36 +190,15 @@ struct SceneArgs {
     int32_t base_col = -1;   // scene planar base (x, y, theta) columns, -1: none
     int32_t uniform = 0;     // 1: every sample uses the scene column values of sample 0
 };
-// The group frames of a lane: in registers (12 per group), or with LF in LDS slots of the lane
-// (element (g, j) at lf[(g * 12 + j) * B]: consecutive lanes, no bank conflicts) -- the specialised fp32
-// door-sweep kernel, whose 2 x 12 frame registers are what keeps it at 4 waves per SIMD (KINHIP_SCENE_LDS)
-template <typename T, int MAXG, bool LF = false>
+// The group frames of a lane, in registers (12 per group).  (Measured and not kept: the frames in LDS, 115 -> 103
+// VGPRs, still 4 waves per SIMD, door sweep 130 -> 143 us; with 5 waves forced, 7 VGPR spills, 144 us --
+// profiles/r05_scene_lds_ab.txt)
+template <typename T, int MAXG>
 struct SceneCtx {
     KSceneGroup gr[MAXG];  // the groups' descriptors, loaded once (uniform: scalar registers)
     int ng;
-    T inv[LF ? 1 : MAXG][12];  // per lane: world -> group frame (row-major 3x4); MAXG >= ng (register budget)
-    __attribute__((address_space(3))) T* lf = nullptr;
-    int B = 0;
-    __device__ __forceinline__ T at(int g, int j) const {
-        if constexpr (LF) return lf[(g * 12 + j) * B];
-        else return inv[g][j];
-    }
-    __device__ __forceinline__ void set(int g, int j, T v) {
-        if constexpr (LF) lf[(g * 12 + j) * B] = v;
-        else inv[g][j] = v;
-    }
+    T inv[MAXG][12];  // per lane: world -> group frame (row-major 3x4); MAXG >= ng (register budget)
 };
-// (measured and not kept: the frames in LDS, 115 -> 103 VGPRs, still 4 waves per SIMD, door sweep 130 -> 143 us;
-// with 5 waves forced, 7 VGPR spills, 144 us -- profiles/r05_scene_lds_ab.txt.  A/B build: KINHIP_SCENE_LDS=1)
-#ifndef KINHIP_SCENE_LDS
-#define KINHIP_SCENE_LDS 0
-#endif
-// whether a scene kernel of `scene_groups` groups keeps the lane frames in LDS, after the boxes (kinhip_coll.hip
-// sizes the launch: 12 * scene_groups * blockDim values)
-template <typename T>
-__host__ __device__ constexpr bool scene_frames_in_lds(int scene_groups) {
-    return KINHIP_SCENE_LDS && sizeof(T) == 4 && scene_groups > 0 && scene_groups <= 2;
-}
 
 // rotation by th about the unit axis u (Rodrigues; the reference's UnitQuaternion(cos th/2, u sin th/2)).
 // fmaz / mul0: with the axis a compile-time constant (kin_plan_specialize_scene) a coordinate axis leaves
@@ -237,8 +214,8 @@ __device__ __forceinline__ void axis_rotation(const T* __restrict__ u, T th, T (
 }
 
 // the group frames of this sample (get_transform(scene, link) up to the group's moving frame), inverted
-template <typename T, int MAXG, bool LF>
-__device__ __forceinline__ void scene_frames(SceneCtx<T, MAXG, LF>& sc, const SceneArgs<T>& sa, uint32_t off) {
+template <typename T, int MAXG>
+__device__ __forceinline__ void scene_frames(SceneCtx<T, MAXG>& sc, const SceneArgs<T>& sa, uint32_t off) {
     sc.ng = sa.ng;
     const uint32_t so = sa.uniform ? 0u : off;
 #pragma unroll
@@ -277,16 +254,16 @@ __device__ __forceinline__ void scene_frames(SceneCtx<T, MAXG, LF>& sc, const Sc
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
 #pragma unroll
-            for (int j = 0; j < 3; ++j) sc.set(g, 4 * i + j, f.r[3 * j + i]);
-            sc.set(g, 4 * i + 3, -fmaz(f.r[i], f.t[0], fmaz(f.r[3 + i], f.t[1], mul0z(f.r[6 + i], f.t[2]))));
+            for (int j = 0; j < 3; ++j) sc.inv[g][4 * i + j] = f.r[3 * j + i];
+            sc.inv[g][4 * i + 3] = -fmaz(f.r[i], f.t[0], fmaz(f.r[3 + i], f.t[1], mul0z(f.r[6 + i], f.t[2])));
         }
     }
 }
 
 // UnionSDF over the scene's groups: each group's boxes in its own frame (union_sdf), the first minimum
 // over groups; the gradient rotated back to the world
-template <typename T, bool GRAD, int NS, int MAXG, bool LF>
-__device__ __forceinline__ void scene_union(const SceneCtx<T, MAXG, LF>& sc, const KBox<T>* __restrict__ boxes,
+template <typename T, bool GRAD, int NS, int MAXG>
+__device__ __forceinline__ void scene_union(const SceneCtx<T, MAXG>& sc, const KBox<T>* __restrict__ boxes,
                                             const KAabb<T>* __restrict__ aabb, const T (&px)[NS], const T (&py)[NS],
                                             const T (&pz)[NS], T (&d)[NS], T (&gw)[NS][3], const unsigned char* smem,
                                             bool use_lds) {
@@ -304,7 +281,7 @@ __device__ __forceinline__ void scene_union(const SceneCtx<T, MAXG, LF>& sc, con
         const KSceneGroup& G = sc.gr[g];
         T I[12];
 #pragma unroll
-        for (int j = 0; j < 12; ++j) I[j] = sc.at(g, j);
+        for (int j = 0; j < 12; ++j) I[j] = sc.inv[g][j];
         T lx[NS], ly[NS], lz[NS];
         // Exact cull: every box of the group lies in its enclosing box (bc, bh), so the distance to that
         // box is a lower bound of the group's distance; a group that cannot come below the minimum of the
@@ -349,18 +326,13 @@ __device__ __forceinline__ void scene_union(const SceneCtx<T, MAXG, LF>& sc, con
         for (int i = 0; i < NS; ++i) {
             if (wg[i] < 0) continue;  // no group below +inf (NaN input): a zero gradient
             T I[12];
-            if constexpr (LF) {  // the winning group's frame: one LDS read per entry at the lane's own index
 #pragma unroll
-                for (int j = 0; j < 12; ++j) I[j] = sc.at(wg[i], j);
-            } else {
+            for (int j = 0; j < 12; ++j) I[j] = sc.inv[0][j];
 #pragma unroll
-                for (int j = 0; j < 12; ++j) I[j] = sc.inv[0][j];
+            for (int g = 1; g < MAXG; ++g) {
+                if (g >= sc.ng) break;  // uniform
 #pragma unroll
-                for (int g = 1; g < MAXG; ++g) {
-                    if (g >= sc.ng) break;  // uniform
-#pragma unroll
-                    for (int j = 0; j < 12; ++j) I[j] = wg[i] == g ? sc.inv[g][j] : I[j];
-                }
+                for (int j = 0; j < 12; ++j) I[j] = wg[i] == g ? sc.inv[g][j] : I[j];
             }
             const T lx = fmaz(I[0], px[i], fmaz(I[1], py[i], fmaz(I[2], pz[i], I[3])));
             const T ly = fmaz(I[4], px[i], fmaz(I[5], py[i], fmaz(I[6], pz[i], I[7])));
@@ -381,16 +353,6 @@ __device__ __forceinline__ void scene_union(const SceneCtx<T, MAXG, LF>& sc, con
 #define KINHIP_COLL_PAIRS 1
 #endif
 
-// Paired gradient stores (A/B knob, specialised fp32 kernels only): the two lanes of a pair swap one
-// value and each writes two configurations of one row with a 64-bit store (rows c and c + 1 of a
-// sphere), half the store instructions of one row per lane.  Full waves, ndof <= 16, even ld only.
-#ifndef KINHIP_COLL_STPAIR
-#define KINHIP_COLL_STPAIR 0
-#endif
-#ifndef KINHIP_JIT
-#define KINHIP_JIT 0
-#endif
-
 // SCENE: 0 = a static union; else the union is attached to a scene with at most SCENE moving groups
 // (the per-lane group frames take 12 registers per group, so kernels come for 2 and kMaxSceneGroups)
 template <typename T, int MAXA, bool GRAD, int SCENE = 0>
@@ -402,11 +364,8 @@ __device__ __forceinline__ void coll_spheres(int s_last, int k0, int k1, const F
                                              uint32_t off, T* __restrict__ dists, int64_t ldd,
                                              T* __restrict__ grads, int64_t ldg, T& dmin,
                                              const unsigned char* smem, bool use_lds,
-                                             const SceneCtx<T, SCENE ? SCENE : 1, scene_frames_in_lds<T>(SCENE)>* sc = nullptr) {
+                                             const SceneCtx<T, SCENE ? SCENE : 1>* sc = nullptr) {
     const int ndof = P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
-    // paired stores (KINHIP_COLL_STPAIR): every lane of the wave active, rows 8-byte aligned
-    const bool pair_ok = GRAD && KINHIP_COLL_STPAIR && grads && (ldg & 1) == 0 &&
-                         (((uint64_t)grads) & 7u) == 0 && __ballot(1) == ~0ull;
     // sphere centre in the world (fmz: in specialised kernels the centre is a constant, often with
     // zero components)
     auto centre = [&](const KSphere<T>& sp, T& px, T& py, T& pz) {
@@ -442,53 +401,6 @@ __device__ __forceinline__ void coll_spheres(int s_last, int k0, int k1, const F
         d -= offs;  // IneqConst: dist - margin (src/planning.jl:66)
         dmin = fmin(dmin, d);
         if (dists) KIN_CO_ST(dists, sp.out, ldd, off, d);
-        if constexpr (GRAD && KINHIP_COLL_STPAIR && KINHIP_JIT && sizeof(T) == 4) {
-            constexpr int NC = 16;
-            if (ndof <= NC && pair_ok) {  // uniform
-                const int64_t r0 = (int64_t)sp.out * ndof;
-                T cv[NC];
-#pragma unroll
-                for (int c = 0; c < NC; ++c) cv[c] = T(0);  // and the columns that cannot move this chain
-                const T w0 = fma(py, g[2], -(pz * g[1])), w1 = fma(pz, g[0], -(px * g[2])), w2 = fma(px, g[1], -(py * g[0]));
-#pragma unroll
-                for (int j = 0; j < MAXA; ++j) {
-                    if (S[j].flags & SF_REC) {
-                        T v = T(0);
-                        if (j <= s_last && !cut) {
-                            if (S[j].jkind == MOT_PRISM)
-                                v = fma(g[0], rz[j][0], fma(g[1], rz[j][1], g[2] * rz[j][2]));
-                            else
-                                v = fma(rz[j][0], w0, fma(rz[j][1], w1, fma(rz[j][2], w2,
-                                    -fma(g[0], rm[j][0], fma(g[1], rm[j][1], g[2] * rm[j][2])))));
-                        }
-#pragma unroll
-                        for (int c = 0; c < NC; ++c)
-                            if ((S[j].colmask >> c) & 1ull) cv[c] = v;
-                    }
-                }
-                if (P.flags & PF_BASE) {
-#pragma unroll
-                    for (int c = 0; c < NC; ++c) {
-                        if (c == P.n_jac) cv[c] = cut ? T(0) : g[0];
-                        if (c == P.n_jac + 1) cv[c] = cut ? T(0) : g[1];
-                        if (c == P.n_jac + 2) cv[c] = cut ? T(0) : fma(-g[0], py - by, g[1] * (px - bx));
-                    }
-                }
-                const int par = (int)(threadIdx.x & 1u);
-#pragma unroll
-                for (int c = 0; c < NC; c += 2) {
-                    if (c + 1 < ndof) {
-                        const T send = par ? cv[c] : cv[c + 1];
-                        const T recv = __shfl_xor(send, 1);
-                        KIN_CO_ST2(grads, r0 + c + par, ldg, off - (uint32_t)par * 4u, par ? recv : cv[c],
-                                par ? cv[c + 1] : recv);
-                    } else if (c < ndof) {
-                        KIN_CO_ST(grads, r0 + c, ldg, off, cv[c]);
-                    }
-                }
-                return;
-            }
-        }
         if (GRAD) {
             const int64_t r0 = (int64_t)sp.out * ndof;
             uint64_t zm = P.zmask;  // q columns that cannot move this chain: 0
@@ -598,14 +510,7 @@ __device__ __forceinline__ void coll_body(const KProg<T>& P, const KStep<T>* __r
     const T trunc = (T)a.truncation;
     const T offs = (T)a.offset;
     const bool broad = SCENE == 0 && isfinite(a.truncation);  // uniform (attached boxes: no union bound)
-    constexpr bool LFS = scene_frames_in_lds<T>(SCENE);
-    SceneCtx<T, SCENE ? SCENE : 1, LFS> sc;
-    if constexpr (LFS) {  // this lane's frame slots after the boxes (the launcher sizes the LDS)
-        const int boff = use_lds ? (a.n_boxes * (int)sizeof(KBox<T>) + 15) / 16 * 16 : 0;
-        sc.lf = (__attribute__((address_space(3))) T*)((__attribute__((address_space(3))) unsigned char*)smem + boff) +
-                threadIdx.x;
-        sc.B = (int)blockDim.x;
-    }
+    SceneCtx<T, SCENE ? SCENE : 1> sc;
     if constexpr (SCENE != 0) scene_frames(sc, sa, off);  // (plain SoA only: kin_coll_batch_scene)
     const T bnd[6] = {(T)a.bc[0], (T)a.bc[1], (T)a.bc[2], (T)a.bh[0], (T)a.bh[1], (T)a.bh[2]};
     T dmin = T(INFINITY);

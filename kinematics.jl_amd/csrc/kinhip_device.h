@@ -71,13 +71,6 @@ template <typename T>
 struct SinCosV {
     T s, c;
 };
-#ifndef KINHIP_NOCALL_TRIG
-#define KINHIP_NOCALL_TRIG 0  // 1 (A/B fault probe only): no out-of-line call; |x| beyond the bound -> NaN
-#endif
-#if KINHIP_NOCALL_TRIG
-__device__ __forceinline__ SinCosV<float> sincos_slow(float) { return {__builtin_nanf(""), __builtin_nanf("")}; }
-__device__ __forceinline__ SinCosV<double> sincos_slow(double) { return {__builtin_nan(""), __builtin_nan("")}; }
-#else
 __device__ __noinline__ SinCosV<float> sincos_slow(float x) {
     float s, c;
     sincosf(x, &s, &c);
@@ -88,7 +81,6 @@ __device__ __noinline__ SinCosV<double> sincos_slow(double x) {
     sincos(x, &s, &c);
     return {s, c};
 }
-#endif
 
 __device__ __forceinline__ void sincos_t(float x, float* s, float* c) {
     if (__builtin_expect(!(fabsf(x) < 8192.0f), 0)) {
@@ -211,11 +203,6 @@ __device__ __forceinline__ double ld_soa(const double* __restrict__ base, int64_
 __device__ __forceinline__ void st_soa(float* __restrict__ base, int64_t row, int64_t ld, uint32_t off, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(base + row * ld), (int)off, 0, KINHIP_STORE_AUX);
 }
-// two consecutive configurations of one row (8 bytes at off, 8-byte aligned)
-__device__ __forceinline__ void st_soa2(float* __restrict__ base, int64_t row, int64_t ld, uint32_t off, float lo, float hi) {
-    __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(lo), __float_as_uint(hi)}, row_rsrc(base + row * ld),
-                                          (int)off, 0, KINHIP_STORE_AUX);
-}
 __device__ __forceinline__ void st_soa(double* __restrict__ base, int64_t row, int64_t ld, uint32_t off, double v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), row_rsrc(base + row * ld), (int)off, 0,
                                           KINHIP_STORE_AUX);
@@ -257,11 +244,6 @@ __device__ __forceinline__ double ldo_soa(const double* __restrict__ base, int64
 __device__ __forceinline__ void sto_soa(float* __restrict__ base, int64_t row, int64_t ld, uint32_t off, float v) {
     __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), row_rsrc(base), (int)off, (int)(row * ld * 4),
                                           KINHIP_STORE_AUX);
-}
-__device__ __forceinline__ void sto_soa2(float* __restrict__ base, int64_t row, int64_t ld, uint32_t off, float lo,
-                                         float hi) {
-    __builtin_amdgcn_raw_buffer_store_b64(u32x2{__float_as_uint(lo), __float_as_uint(hi)}, row_rsrc(base), (int)off,
-                                          (int)(row * ld * 4), KINHIP_STORE_AUX);
 }
 __device__ __forceinline__ void sto_soa(double* __restrict__ base, int64_t row, int64_t ld, uint32_t off, double v) {
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, v), row_rsrc(base), (int)off, (int)(row * ld * 8),
@@ -574,21 +556,10 @@ __device__ __forceinline__ void emit_jcol(const JacCtx<T>& J, const KStep<T>& st
     }
 }
 
-// Block -> configuration chunk.  Workgroups are dispatched round-robin over the
-// 8 XCDs (block b on XCD b % 8); with KINHIP_XCD_REMAP each XCD instead takes
-// one contiguous eighth of the batch, so its L2 and DRAM pages see sequential
-// row segments rather than every eighth 1 KB piece.
-#ifndef KINHIP_XCD_REMAP
-#define KINHIP_XCD_REMAP 0
-#endif
-__device__ __forceinline__ uint32_t config_block() {
-#if KINHIP_XCD_REMAP
-    const uint32_t nb = gridDim.x, b = blockIdx.x, x = b & 7u, q = nb >> 3, r = nb & 7u;
-    return x * q + (x < r ? x : r) + (b >> 3);
-#else
-    return blockIdx.x;
-#endif
-}
+// Block -> configuration chunk: workgroups are dispatched round-robin over the 8 XCDs (block b on XCD
+// b % 8).  (Measured and not kept: each XCD taking one contiguous eighth of the batch, 2^22 configurations
+// 168 -> 194 us; profiles/r01_row_pad_probe.txt)
+__device__ __forceinline__ uint32_t config_block() { return blockIdx.x; }
 
 inline unsigned grid_of(int64_t n, int block) { return (unsigned)((n + block - 1) / block); }
 

@@ -212,7 +212,7 @@ hipError_t launch_ik_dls(const KProg<T>& P, const KStep<T>* steps, const LaunchG
             // lane group that takes its next target runs those iterations while the rest of the wave is in
             // fp32, so nearly every wave iteration pays both solves.  The plain grid starts a wave's targets
             // together (1M targets: 0.607 -> 0.502 ms, identical results; profiles/r05_ik_1m_queue_ab.txt)
-            if (sizeof(T) == 4 && KINHIP_IK_F64SOLVE == 3 && KINHIP_IK_F64_ITERS > 0 && tpq_env < 0 && qmode < 0)
+            if (sizeof(T) == 4 && KINHIP_IK_F64_ITERS > 0 && tpq_env < 0 && qmode < 0)
                 q1 = false;
             if (q1 && tpq_env < 0 && qmode < 0 && jf) {
                 const hipFunction_t f1 = jf->ik[a.with_rot == 2 ? 2 : a.with_rot ? 1 : 0][0];
@@ -265,8 +265,8 @@ hipError_t launch_ik_dls(const KProg<T>& P, const KStep<T>* steps, const LaunchG
             // that iteration and lambda is not below the threshold: its specialised form without that code
             // (F64S = false; the same arithmetic) then runs -- config 4 0.072-0.074 -> 0.070 ms on one box,
             // identical results (profiles/r06_ik_p2_nof64_ab.txt)
-            const bool no_f64 = sizeof(T) == 4 && KINHIP_IK_F64SOLVE == 3 &&
-                                !(at.lam2 < T(KINHIP_IK_F32SOLVE_MIN_LAM2)) && (cut == 0 || cut >= KINHIP_IK_F64_ITERS);
+            const bool no_f64 = sizeof(T) == 4 && !(at.lam2 < T(KINHIP_IK_F32SOLVE_MIN_LAM2)) &&
+                                (cut == 0 || cut >= KINHIP_IK_F64_ITERS);
             if ((e = one(a2, G2, s0, c, ng2, (c + ng2 - 1) / ng2, bs2, no_f64)) != hipSuccess) {
                 // phase 1 ran but phase 2 did not move the next call's start mark: restart the ring;
                 // the targets phase 1 did not solve keep undefined outputs (kin_ik_dls_batch says so)

@@ -16,30 +16,19 @@ namespace {
 #ifndef KINHIP_IK_FAST_ATAN
 #define KINHIP_IK_FAST_ATAN 1  // fp32: polynomial atan2 for the rotation error's angle (rot_error)
 #endif
-// fp32: the damped solve (J W J^T + lambda^2 I, its Cholesky, the two triangular solves and dq = J^T y)
-// in fp64 from the fp32 Jacobian.  Forming J J^T in fp32 errs by ~eps |J|^2 = 2.4e-7 against
-// lambda^2 = 1e-4, and at a singular arm (Fetch at q = 0: rank 4) y carries ~e / lambda^2 in the null
-// directions that J^T y cancels: an fp32 solve moves dq by up to 2e-3 rad against the fp64 oracle's,
-// the J rounding alone by 1e-6 (tools/ik_fp32_solve_error.py).  0: the fp32 solve (A/B build).  2: the
-// fp32 factorisation and solve plus one step of iterative refinement whose residual
-// e - (J W J^T + lambda'^2 I) y is formed in fp64 from J itself (J^T y, then J (W J^T y)), never from
-// the rounded J J^T: the fp32 factor contracts the error by ~eps kappa ~ 1e-3 per step.  3: the fp64
-// solve for the first KINHIP_IK_F64_ITERS iterations of attempt 0 only -- the attempt that starts from
-// the caller's q0, which for config 4 (and any caller starting from a zero / home pose) is a singular
-// arm (Fetch at q = 0: rank 4) -- and the fp32 solve everywhere else.  Along config-4 trajectories the
-// fp32 solve's step error (fp32 normal equations vs fp64, the same fp32 J) is <= 8.4e-4 at iteration 0,
-// 5.5e-4 at 1, 4.3e-4 at 2 and <= 1.8e-4 from iteration 3 on, 99.4% of the lanes <= 1e-5 there; restart
-// attempts start from random angles (tools/ik_cond_explore.py).  The choice is a function of the lane's
-// own attempt and iteration, so every lane layout / schedule still gives identical results, and phase 1
-// of the two-phase schedule (every lane at the same iteration) takes one path per wave.
-#ifndef KINHIP_IK_F64SOLVE
-#define KINHIP_IK_F64SOLVE 3
-#endif
+// fp32: the damped solve (J W J^T + lambda^2 I, its Cholesky, the two triangular solves and dq = J^T y) runs
+// in fp64 from the fp32 Jacobian for the first KINHIP_IK_F64_ITERS iterations of attempt 0 only, and in fp32
+// everywhere else.  Attempt 0 starts from the caller's q0, which for config 4 (and any caller starting from a
+// zero / home pose) is a singular arm (Fetch at q = 0: rank 4): there y carries ~e / lambda^2 in the null
+// directions that J^T y cancels, and an fp32 solve moves dq by up to 2e-3 rad against the fp64 oracle's
+// (tools/ik_fp32_solve_error.py).  Along config-4 trajectories the fp32 solve's step error is <= 1.8e-4 from
+// iteration 3 on, and restart attempts start from random angles (tools/ik_cond_explore.py).  The choice is a
+// function of the lane's own attempt and iteration, so every lane layout / schedule gives identical results.
 #ifndef KINHIP_IK_F64_ITERS
 #define KINHIP_IK_F64_ITERS 3
 #endif
-// ... and with KINHIP_IK_F64SOLVE = 3 the fp64 solve everywhere when lambda^2 is below this: the
-// analysis above rests on lambda^2 = 1e-4 against the fp32 normal equations' ~eps |J|^2 = 2.4e-7; a smaller
+// ... and the fp64 solve everywhere when lambda^2 is below this: the analysis above rests on
+// lambda^2 = 1e-4 against the fp32 normal equations' ~eps |J|^2 = 2.4e-7; a smaller
 // damping (down to lambda = 0, which kin_ik_params accepts) leaves the fp32 factorisation of a near-singular
 // arm without that margin (NaN pivots at lambda = 0).  A uniform kernel argument: one path per wave.
 #ifndef KINHIP_IK_F32SOLVE_MIN_LAM2
@@ -174,15 +163,6 @@ __device__ __forceinline__ void rot_error(const T (&Rt)[9], const T (&R)[9], T (
         for (int k = 0; k < 3; ++k) w[k] = a[k] / nn * th;
     }
 }
-
-template <bool F32>
-struct ik_solve_type {
-    using type = double;
-};
-template <>
-struct ik_solve_type<true> {
-    using type = float;
-};
 
 template <typename T>
 struct IkArgsT {
@@ -624,11 +604,9 @@ __device__ __forceinline__ void ik_body(const KProg<T>& P, const KStep<T>* __res
         // (the re-solve ran in ~half of all lane-iterations, i.e. in nearly every wave-iteration).
         T dq[MAXA], db[3] = {T(0), T(0), T(0)};
         T mx = T(0);
-        // the damped solve in arithmetic type TS: fp64 (also in the fp32 kernel, KINHIP_IK_F64SOLVE)
+        // the damped solve in arithmetic type TS: fp64, or fp32 in the fp32 kernel (KINHIP_IK_F64_ITERS)
         auto damped_solve = [&](auto ts_tag) {
             using TS = decltype(ts_tag);
-            constexpr bool refine = sizeof(T) == 4 && KINHIP_IK_F64SOLVE == 2;
-            using YS = typename ik_solve_type<!refine && sizeof(TS) == 4>::type;  // type of the solution y
             TS Jb[3][ROWS];
             if (base) {
 #pragma unroll
@@ -768,56 +746,20 @@ __device__ __forceinline__ void ik_body(const KProg<T>& P, const KStep<T>* __res
 #pragma unroll
             for (int r = 0; r < ROWS; ++r) e_s[r] = (TS)e[r];
             chol_solve(e_s, y0);
-            YS y[ROWS];
+            TS y[ROWS];  // (a plain copy: solving into y directly reorders the generic kernels' instructions)
 #pragma unroll
-            for (int r = 0; r < ROWS; ++r) y[r] = (YS)y0[r];
-            if constexpr (refine) {
-                // r = e - lambda'^2 y - J W (J^T y) - Jb Jb^T y in fp64, from the weighted columns of A
-                double res[ROWS];
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) res[r] = fma(-(double)lam2, y[r], (double)e[r]);
-#pragma unroll
-                for (int s = 0; s < MAXA; ++s) {
-                    T J[ROWS];
-                    jcol_pre<T, ROWS>(S[s], ro[s], rz[s], J);
-                    if ((S[s].flags & SF_REC) && S[s].qcol >= 0 && ((blk >> s) & 1u)) continue;  // held: W = 0
-                    const int nr = (ROWS == 6 && S[s].jkind == MOT_PRISM) ? 3 : ROWS;
-                    double u = 0.0;
-#pragma unroll
-                    for (int r = 0; r < ROWS; ++r)
-                        if (r < nr) u = fma((double)J[r], y[r], u);
-#pragma unroll
-                    for (int r = 0; r < ROWS; ++r)
-                        if (r < nr) res[r] = fma(-(double)J[r], u, res[r]);
-                }
-                if (base) {
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) {
-                        double u = 0.0;
-#pragma unroll
-                        for (int r = 0; r < ROWS; ++r) u = fma((double)Jb[k][r], y[r], u);
-#pragma unroll
-                        for (int r = 0; r < ROWS; ++r) res[r] = fma(-(double)Jb[k][r], u, res[r]);
-                    }
-                }
-                TS rs[ROWS], dl[ROWS];
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) rs[r] = (TS)res[r];
-                chol_solve(rs, dl);
-#pragma unroll
-                for (int r = 0; r < ROWS; ++r) y[r] = y[r] + (YS)dl[r];
-            }
+            for (int r = 0; r < ROWS; ++r) y[r] = (TS)y0[r];
             KIN_IK_STAMP(4);
             uint32_t nb = 0;
 #pragma unroll
             for (int s = 0; s < MAXA; ++s) {
                 T J[ROWS];
                 jcol_pre<T, ROWS>(S[s], ro[s], rz[s], J);
-                YS vs = YS(0);
+                TS vs = TS(0);
                 const int nr = (ROWS == 6 && S[s].jkind == MOT_PRISM) ? 3 : ROWS;  // (zero angular rows)
 #pragma unroll
                 for (int r = 0; r < ROWS; ++r)
-                    if (r < nr) vs = fma((YS)J[r], y[r], vs);
+                    if (r < nr) vs = fma((TS)J[r], y[r], vs);
                 const T v = (T)vs;
                 const bool held = (blk >> s) & 1u;
                 dq[s] = held ? T(0) : v;
@@ -830,25 +772,25 @@ __device__ __forceinline__ void ik_body(const KProg<T>& P, const KStep<T>* __res
             if (base) {
 #pragma unroll
                 for (int k = 0; k < 3; ++k) {
-                    YS v = YS(0);
+                    TS v = TS(0);
 #pragma unroll
-                    for (int r = 0; r < ROWS; ++r) v = fma((YS)Jb[k][r], y[r], v);
+                    for (int r = 0; r < ROWS; ++r) v = fma(Jb[k][r], y[r], v);
                     db[k] = (T)v;
                     mx = fmax(mx, fabs(db[k]));
                 }
             }
         };
-        if constexpr (sizeof(T) == 4 && KINHIP_IK_F64SOLVE == 3) {
-            // fp64 for the first iterations of attempt 0 (the caller's q0), fp32 elsewhere (see the macro).  F64S =
-            // false: a launch where that never holds (phase 2 of the two-phase schedule with a hand-over point of at
-            // least KINHIP_IK_F64_ITERS and lambda^2 >= KINHIP_IK_F32SOLVE_MIN_LAM2; launch_ik_dls) compiles the fp64
-            // solve out -- the same arithmetic, without its code and registers in the loop
+        if constexpr (sizeof(T) == 4) {
+            // fp64 for the first iterations of attempt 0 (the caller's q0), fp32 elsewhere (KINHIP_IK_F64_ITERS).
+            // F64S = false: a launch where that never holds (phase 2 of the two-phase schedule with a hand-over
+            // point of at least KINHIP_IK_F64_ITERS and lambda^2 >= KINHIP_IK_F32SOLVE_MIN_LAM2; launch_ik_dls)
+            // compiles the fp64 solve out -- the same arithmetic, without its code and registers in the loop
             if (F64S && ((att == 0 && it < KINHIP_IK_F64_ITERS) || a.lam2 < T(KINHIP_IK_F32SOLVE_MIN_LAM2)))
                 damped_solve(double());
             else
                 damped_solve(float());
         } else {
-            damped_solve(typename ik_solve_type<sizeof(T) == 4 && KINHIP_IK_F64SOLVE != 1>::type());
+            damped_solve(double());
         }
         KIN_IK_STAMP(5);
         const T sc = mx > a.max_step ? a.max_step / mx : T(1);

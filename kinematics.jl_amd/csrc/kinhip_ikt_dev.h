@@ -24,13 +24,6 @@
 #pragma clang fp contract(on)
 #endif
 
-// the specialised kernels unroll the tree walk and the sphere loops (constant trip counts)
-#ifdef KINHIP_JIT
-#define KIN_IKT_UNROLL _Pragma("unroll")
-#else
-#define KIN_IKT_UNROLL
-#endif
-
 // Diagnostic section stamps (tools only: KINHIP_JIT_DEFS=-DKINHIP_IKT_SECT=<k> in the A/B build,
 // tools/ikt_sect.py): the cycles of iteration section k (1 tree walk, 2 sphere distances + rows, 3 rows into
 // the normal equations, 4 pose error + checks, 5 pose rows, 6 factorisation + solves, 7 step + loop top)
@@ -93,19 +86,6 @@ __device__ __forceinline__ T pick_lane(const T (&a)[N], int i) {
         for (int k = 0; k < (1 << (B - 1 - b)); ++k) t[k] = bit ? t[2 * k + 1] : t[2 * k];
     }
     return t[0];
-}
-template <int V>
-struct IntC {
-    static constexpr int value = V;
-};
-// a[O + i] for a per-lane i in [0, S) (a lane's row of the O-th round of S rows; O + i >= N gives a[N - 1])
-template <int O, int S, typename T, int N>
-__device__ __forceinline__ T pick_round(const T (&a)[N], int i) {
-    constexpr int M = N - O < S ? N - O : S;  // rows of this round that exist
-    T sub[M > 0 ? M : 1];
-#pragma unroll
-    for (int k = 0; k < (M > 0 ? M : 1); ++k) sub[k] = a[M > 0 ? O + k : N - 1];
-    return pick_lane(sub, i);
 }
 template <typename T, int N>
 __device__ __forceinline__ void put(T (&a)[N], int i, T v) {
@@ -334,13 +314,6 @@ __device__ __forceinline__ void ikt_start(const KIkcProg<T>& P, const IkArgsT<T>
 // returns the best point it found.  NR: rounds of spheres per lane (ceil(n_sph / S); S > 1 only in
 // the specialised kernels, where the program is constant).  MAXG > 0: boxes attached to a scene,
 // one set of scene joint values per target (sa).
-// S > 1: the rows of the normal equations formed by every lane of the group (0) or owned by the group's lanes
-// and gathered (1; A/B: KINHIP_JIT_DEFS=-DKINHIP_IKT_OWN=1) -- identical results.  Ownership cuts the loop's
-// FMAs 1,140 -> 658 (offline ISA) and yet measured slower on every leg (stage 2 of f3 0.152 -> 0.231 ms, the
-// scene door 0.198 -> 0.349, PR2 0.67 -> 2.29; profiles/r05_ikt_own_ab.txt): not kept
-#ifndef KINHIP_IKT_OWN
-#define KINHIP_IKT_OWN 0
-#endif
 // S > 1 (default): the normal equations distributed over the group's lanes through LDS.  Each sphere lane
 // stores its rows (w^2 a, a, viol), every lane the pose rows J (and e); lane sl then forms the entries sl,
 // sl + S, ... of the system -- entry (r, c) = sum over the in-band spheres, in sphere order, of
@@ -446,7 +419,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
     // eC = MAXV: the right-hand side; entries past NE are read but never stored)
     // (trees of at most 12 variables: a two-arm tree's dense system of 170 entries measured 0.68 -> 0.91 ms
     // on PR2, whose replicated form folds the arms' structural zeros away)
-    constexpr bool LNE = S > 1 && MAXV <= 12 && !(KINHIP_IKT_OWN) && KINHIP_IKT_LDSNE;
+    constexpr bool LNE = S > 1 && MAXV <= 12 && KINHIP_IKT_LDSNE;
     using NL = IktNe<MAXV, ROWS, (NR > 0 ? NR : 1) * S>;
     constexpr int NJ = LNE ? (NL::NE + S - 1) / S : 1;
     T* ne_reg = nullptr;
@@ -504,21 +477,6 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
 #pragma unroll
             for (int c = 0; c < MAXV; ++c) A[r][c] = T(0);
         }
-        // S > 1: the rows of the normal equations are accumulated by their owners -- lane sl of an attempt group
-        // owns rows v = sl, sl + S, ... (Ao[o] = row o S + sl, bo[o] its right-hand side) -- and gathered into A /
-        // bv for the (replicated) factorisation.  Each entry gets the same FMAs in the same order as the one-lane
-        // kernel (spheres in order, then the pose rows), so the results are bit-identical for every S; a group's
-        // lanes no longer each form every entry (the sphere rows and the pose rows were ~2/3 of the FMAs of an
-        // iteration, on the one-wave critical path of the batch's slowest target).
-        constexpr bool OWN = S > 1 && KINHIP_IKT_OWN;
-        constexpr int NRO = OWN ? (MAXV + S - 1) / S : 1;
-        T Ao[NRO][MAXV], bo[NRO];
-#pragma unroll
-        for (int o = 0; o < NRO; ++o) {
-            bo[o] = T(0);
-#pragma unroll
-            for (int c = 0; c < MAXV; ++c) Ao[o][c] = T(0);
-        }
         dmin = T(INFINITY);
         // S > 1: this lane's sphere of each round (centre, radius, the variables moving it)
         T pc[NR > 0 ? NR : 1][3], prad[NR > 0 ? NR : 1];
@@ -532,7 +490,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
             }
         }
         auto spheres = [&](const Fr<T>& f, int k0, int k1) {
-            KIN_IKT_UNROLL
+#pragma unroll
             for (int k = k0; k < k1; ++k) {
                 const KSphere<T>& sp = sph[k];
                 const uint32_t anc = sp.anc;
@@ -565,7 +523,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
             }
         };
         spheres(root, P.sph_root0, P.sph_root1);
-        KIN_IKT_UNROLL
+#pragma unroll
         for (int s = 0; s < P.nS; ++s) {
             const KIkcStep<T>& st = St[s];
             if (st.parent == kIkcRoot) cur = root;
@@ -634,7 +592,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
                     row[2 * MAXV] = inb ? viol[r] : T(0);
                 }
             }
-            KIN_IKT_UNROLL
+#pragma unroll
             for (int k = 0; k < (LNE ? 0 : P.n_sph); ++k) {
                 const int r = k / S, src = gbase + k % S;
                 const uint32_t anc = sph[k].anc;  // (constant in the specialised kernel)
@@ -653,25 +611,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
 #pragma unroll
                             for (int v = 0; v < MAXV; ++v) ak[v] = ((anc >> v) & 1u) ? bc(av[rr][v]) : T(0);
                         }
-                    if constexpr (!OWN) {
-                        accum_row<T, MAXV>(A, bv, ak, vk, w2, anc);
-                        continue;
-                    }
-                    // this lane's rows (accum_row's operations on them)
-                    auto own = [&](auto oc) {
-                        constexpr int o = decltype(oc)::value;
-                        const int v = o * S + sl;
-                        if (v < MAXV && ((anc >> v) & 1u)) {  // (per lane)
-                            const T wr = w2 * pick_round<o * S, S>(ak, sl);
-                            bo[o] = fma(wr, vk, bo[o]);
-#pragma unroll
-                            for (int c = 0; c < MAXV; ++c)
-                                if ((anc >> c) & 1u) Ao[o][c] = fma(wr, ak[c], Ao[o][c]);
-                        }
-                    };
-                    own(IntC<0>());
-                    if constexpr (NRO > 1) own(IntC<1>());
-                    static_assert(NRO <= 2, "rows per lane (MAXV <= 2 S)");
+                    accum_row<T, MAXV>(A, bv, ak, vk, w2, anc);
                 }
             }
         }
@@ -761,21 +701,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
                                                                             : fma(kr[4], x, fma(kr[5], y, z));
                 else Jr[v] = r == 3 ? x : r == 4 ? y : z;
             }
-            if constexpr (OWN) {  // the owned rows
-                auto own = [&](auto oc) {
-                    constexpr int o = decltype(oc)::value;
-                    const int v = o * S + sl;
-                    if (v < MAXV && ((P.tgt_mask >> v) & 1u)) {  // (per lane)
-                        const T jv = pick_round<o * S, S>(Jr, sl);
-                        bo[o] = fma(jv, e[r], bo[o]);
-#pragma unroll
-                        for (int c = 0; c < MAXV; ++c)
-                            if ((P.tgt_mask >> c) & 1u) Ao[o][c] = fma(jv, Jr[c], Ao[o][c]);
-                    }
-                };
-                own(IntC<0>());
-                if constexpr (NRO > 1) own(IntC<1>());
-            } else if constexpr (LNE) {  // row r of J and e_r (every lane of the group the same values)
+            if constexpr (LNE) {  // row r of J and e_r (every lane of the group the same values)
                 T* jr = ne_reg + NL::JB + r * NL::JW;
 #pragma unroll
                 for (int v = 0; v < MAXV; ++v) jr[v] = Jr[v];
@@ -797,7 +723,7 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
 #pragma unroll
             for (int j = 0; j < NJ; ++j) acc[j] = T(0);
             // (no branch per sphere: its reads then pipeline instead of one LDS round trip per in-band sphere)
-            KIN_IKT_UNROLL
+#pragma unroll
             for (int k = 0; k < P.n_sph; ++k) {
                 const T* row = ne_reg + k * NL::RW;
 #pragma unroll
@@ -821,17 +747,6 @@ __device__ __forceinline__ void ikt_body(const KIkcProg<T>& P, const KIkcStep<T>
 #pragma unroll
                 for (int c = 0; c <= v; ++c) A[v][c] = ar[c];
                 bv[v] = ar[v + 1];
-            }
-        }
-        if constexpr (OWN) {  // gather the owned rows into every lane of the group (structural zeros stay 0)
-#pragma unroll
-            for (int v = 0; v < MAXV; ++v) {
-                const int o = v / S, ow = v % S;
-                auto bc = [&](T x) { return S == 16 ? row_bcast16(x, ow) : lane_bcast(x, gbase + ow); };
-                const uint32_t nz = P.nzrow[v];
-                bv[v] = ((nz >> v) & 1u) ? bc(bo[o]) : T(0);
-#pragma unroll
-                for (int c = 0; c <= v; ++c) A[v][c] = ((nz >> c) & 1u) ? bc(Ao[o][c]) : T(0);
             }
         }
         KIN_IKT_STAMP(5);

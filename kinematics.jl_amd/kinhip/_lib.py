@@ -151,7 +151,7 @@ def lib():
         "kin_plan_specialize_scene": ([P, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
-    # for builds of older sources (tools/ikc_fault_probe.py) that lack newer entry points
+    # for builds of older sources that lack newer entry points
     skip_abi = os.environ.get("KINHIP_SKIP_ABI_CHECK") == "1"
     for name, (args, res) in sig.items():
         if skip_abi and not hasattr(L, name):

@@ -4,7 +4,7 @@ within-limit distribution.
 
   * One damped step from the same seed: |q32 - q64| <= 1e-4, and within the
     perturbation bound delta * |e0| / lambda^2 (delta = 1e-6, the fp32 FK / J gate).  The fp32 kernel
-    solves J W J^T + lambda^2 I in fp64 (KINHIP_IK_F64SOLVE): forming it in fp32 errs by ~eps |J|^2 against
+    solves J W J^T + lambda^2 I in fp64 for attempt 0's first iterations: forming it in fp32 errs by ~eps |J|^2 against
     lambda^2 = 1e-4, which at Fetch's singular q = 0 moved dq by up to 2e-3 (round 3: 1.2e-3 measured).
   * Config-4 settings end to end (fixed lambda, and the bench's error-scaled damping with max_step 1):
     >= 99% of the targets converge in both precisions, >= 98% with
@@ -55,7 +55,7 @@ def test_one_step_within_the_perturbation_bound(setup):
     d = np.abs(Q.double().cpu().numpy() - rq).max(0)
     bound = 1e-6 * e0 / KW["lam"] ** 2
     assert np.all(d <= bound), float((d / bound).max())
-    # the damped solve runs in fp64 from the fp32 Jacobian (KINHIP_IK_F64SOLVE): what is left is the fp32
+    # the damped solve of this first iteration runs in fp64 from the fp32 Jacobian: what is left is the fp32
     # rounding of J itself (~1e-6 at q = 0, tools/ik_fp32_solve_error.py), not the 1/lambda^2 amplification
     # of an fp32 J J^T (2e-3 before)
     print(f"one fp32 step vs fp64: max {d.max():.2e}, p50 {np.median(d):.2e}")

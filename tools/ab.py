@@ -11,11 +11,23 @@ The product library libkinhip.so never reads these variables (kinhip_internal.h 
     e.g. python tools/ab.py ik base KINHIP_IK_TWO_PHASE=0 KINHIP_IK_GROUP=2,KINHIP_IK_TWO_PHASE=0
          python tools/ab.py coll base "KINHIP_JIT_DEFS=-DKINHIP_AABB_UNROLL=1" KINHIP_COLL_FAST_TRIG=0
 
-Knobs (all read only by the A/B build): KINHIP_IK_GROUP, KINHIP_IK_RESIDENT, KINHIP_IK_QUEUE,
-KINHIP_IK_TWO_PHASE, KINHIP_IK_TP_QUEUE (IK schedule), KINHIP_IKC_GROUP (collision-aware IK lanes), KINHIP_FK_PER_LANE (FK grid), KINHIP_JIT_IK_WAVES,
-KINHIP_JIT_COLL_WAVES (occupancy), KINHIP_COLL_FAST_TRIG, KINHIP_IK_FAST_ATAN (arithmetic variants), KINHIP_SCENE_LDS (scene frames in LDS),
-KINHIP_JIT_SLP, KINHIP_JIT_DEFS, KINHIP_JIT_OPTS (compiler options / definitions), KINHIP_JIT_DUMP
-(keep the generated source).  Every run prints its workload's own result line prefixed by the setting."""
+The knobs that exist (this is the one list; tests/test_ab_knobs.py checks every name the tools use against the
+sources).  Environment variables, read only by the A/B build:
+  IK schedule          KINHIP_IK_GROUP, KINHIP_IK_RESIDENT, KINHIP_IK_QUEUE, KINHIP_IK_TWO_PHASE,
+                       KINHIP_IK_TP_QUEUE, KINHIP_IK_P1_CUT, KINHIP_IK_P2_SPREAD,
+                       KINHIP_IK_P2_BLOCK (phase-2 wave placement: measured, block-major stays)
+  collision-aware IK   KINHIP_IKT_S, KINHIP_IKT_G (sphere lanes / attempt groups per target)
+  FK / collision grid  KINHIP_FK_PER_LANE, KINHIP_FK_BLOCK, KINHIP_FK_LDS, KINHIP_COLL_LDS
+  occupancy            KINHIP_JIT_IK_WAVES, KINHIP_JIT_IKT_WAVES, KINHIP_JIT_COLL_WAVES
+  arithmetic variants  KINHIP_COLL_FAST_TRIG, KINHIP_IK_FAST_ATAN
+  compiler             KINHIP_JIT_SLP, KINHIP_JIT_DEFS, KINHIP_JIT_OPTS, KINHIP_JIT_SRC_DIR (device headers read
+                       from a directory)
+  dumps                KINHIP_JIT_DUMP (the generated source), KINHIP_JIT_CODE_DUMP (the code objects)
+Compile-time definitions, through KINHIP_JIT_DEFS for the specialised kernels or `make variant VFLAGS=...` for
+the generic ones: KINHIP_IK_SECT, KINHIP_IKT_SECT (section stamps), KINHIP_IKT_LDSNE, KINHIP_IKT_PK, KINHIP_IK_PK,
+KINHIP_IK_F64_ITERS, KINHIP_IK_F32SOLVE_MIN_LAM2, KINHIP_IK_NARROW, KINHIP_IK_WAVES, KINHIP_COLL_PAIRS,
+KINHIP_COLL_SOFF, KINHIP_AABB_UNROLL, KINHIP_STORE_AUX, KINHIP_CONTRACT_FAST.
+Every run prints its workload's own result line prefixed by the setting."""
 import os
 import subprocess
 import sys

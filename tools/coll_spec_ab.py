@@ -1,6 +1,6 @@
 """Config-5 k_coll timings on the specialised kernels (the bench's legs): min distance, distances +
 gradients on plain SoA rows and on the tiled layout (tile 8192).  Knobs come from the environment
-(KINHIP_COLL_PER_LANE, ...).   python tools/coll_spec_ab.py"""
+(KINHIP_COLL_FAST_TRIG, KINHIP_JIT_COLL_WAVES, ...; tools/ab.py lists them).   python tools/coll_spec_ab.py"""
 import os
 import sys
 import torch

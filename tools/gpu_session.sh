@@ -21,14 +21,14 @@
 #   ik                          config-4 IK timing (product, twice) and 1M targets; per-iteration probe
 #   ik-sections                 iteration section stamps (A/B build, -DKINHIP_IK_SECT=k)
 #   ikt-sections[=<defs>]       collision-aware IK (f3 stage 2) section stamps (A/B build, -DKINHIP_IKT_SECT=k
-#                               plus the given definitions, e.g. ikt-sections=-DKINHIP_IKT_OWN=0)
+#                               plus the given definitions, e.g. ikt-sections=-DKINHIP_IKT_LDSNE=0)
 #   ik-timeline                 per-lane entry / write timeline of one solve (A/B build)
 #   ik-dump                     the specialised IK source (A/B build, KINHIP_JIT_DUMP) + a kernel trace of config 4
 #   coll                        the plain-row padding A/B of the config-5 legs (tools/coll_pad_ab.py)
 #   cik                         the f3 bistage IK leg split by stage, stage 2 on one lane vs 4 (tools/cik_bench.py)
 #   dumps                       the specialised IK (fp32 + fp64) and collision-IK sources (A/B build, KINHIP_JIT_DUMP)
 #   coll-dump                   the specialised collision source (A/B build, KINHIP_JIT_DUMP) for offline ISA
-#   ab=<workload>:<setting>[;<setting>...]   tools/ab.py (A/B build), e.g. ab=ik:base;KINHIP_IK_P2_WAVES=4
+#   ab=<workload>:<setting>[;<setting>...]   tools/ab.py (A/B build), e.g. ab=ik:base;KINHIP_IK_TWO_PHASE=0
 #   pr2-miss[=<n>]              tools/pr2_miss_study.py (PR2 collision-IK leg misses vs host SLSQP)
 #   pr2-alt                     tools/pr2_alt_probe.py (stage-2 step budgets from the manip pose, alt schedules)
 #   scene-const                 door sweep A/B: scene tables as data vs compiled in (tools/scene_ab.py), x3 each,
