@@ -28,7 +28,9 @@
  *    synchronisation inside), with one exception: the first kin_ik_dls_batch
  *    call of a plan that may use the two-phase schedule (restarts > 0, lanes = 0,
  *    <= 2^20 targets) allocates that plan's scratch (synchronising; make it once
- *    outside a stream capture).
+ *    outside a stream capture).  Likewise the first kin_traj_opt_batch call of a plan
+ *    for a new n_wp stages that size's metric table (a small synchronous upload;
+ *    make it once outside a stream capture); later calls are asynchronous.
  *  - Errors: a negative kin_status; kin_last_error() returns a thread-local
  *    message.  Reference exceptions map to: KeyError -> KIN_E_KEY,
  *    MethodError (Jacobian column of a fixed joint) -> KIN_E_METHOD,
@@ -502,6 +504,41 @@ KINHIP_API int kin_ineq_const_batch(const kin_plan* coll_plan, const kin_sdf* sd
 KINHIP_API int kin_pose_const_batch(const kin_plan* p, const void* target, int64_t ldt, const void* q, int64_t ldq,
                                     int64_t n, void* poses, int64_t ldp, void* vals, int64_t ldv, void* jac,
                                     int64_t ldj, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* Batched trajectory optimisation: many plan_trajectory problems             */
+/* (src/planning.jl:332-401) per launch                                       */
+/* ------------------------------------------------------------------------- */
+/* n_traj independent trajectories of n_wp waypoints, the whole descent in one kernel (k_traj).  Minimises the
+ * reference's smoothness objective (Objective, src/planning.jl:1-28: sum_d w_d^2 x_d^T A_sub x_d) plus one-sided
+ * penalties of the IneqConst sphere clearances over the interior waypoints, both end waypoints held fixed (the
+ * two ConfigurationConstraints of construct_problem, :310-330):
+ *     f(X) = sum_d W_d X[:,d]^T A X[:,d] + sum_{w interior} sum_spheres r^2,   r = weight max(0, margin + band - d)
+ * by a covariant (CHOMP-style) projected gradient with backtracking: step = -alpha W^-1 (A[I,I])^-1 g over the
+ * interior waypoints, scaled to max|step| <= max_step, clamped to the joint limits (base columns unbounded);
+ * accepted when f does not increase (then alpha = min(1, 2 alpha); done when f fell by less than ftol and every
+ * interior sphere distance is >= margin - feas), else alpha /= 4 (stalled below 1e-6).  d is kin_coll_batch's
+ * distance with its analytic gradient.  A solver of the build's own (the reference hands the constrained
+ * problem to SLSQP); its fp64 iterates are pinned against a CPU restatement (tests/trajopt_ref.py).
+ * Limits: 3 <= n_wp <= 64; a plan of kin_coll_plan_create whose spheres are one group (one chain) of at most
+ * 16 steps, with at most 12 q columns (+ base) for chains of <= 8 steps, 20 otherwise; a static kin_sdf
+ * (KIN_E_UNSUPPORTED beyond).  kin_plan_specialize leaves this call on its generic kernel. */
+typedef struct kin_traj_params {
+    int32_t n_wp, max_iters;
+    double margin, band, weight, feas;   /* meaning as kin_ik_coll_params */
+    double ftol, max_step;
+    const double* dof_weights;           /* [n_dof(+3)] or NULL = ones (Objective's weights) */
+} kin_traj_params;
+/* xi: [n_dof(+3)][ldx], column t*n_wp + w = waypoint w of trajectory t (IneqConst.eval_batch's layout); in: the
+   initial guess (e.g. the straight line); out: the result; columns w = 0 and n_wp-1 are read, never written.
+   iters: [n_traj] or NULL: the iteration at which a trajectory was done, max_iters + 1 otherwise.
+   info: [4][ldi] (dtype) merit, smoothness term, min sphere distance over the interior waypoints, accepted
+   steps; or NULL. */
+KINHIP_API int kin_traj_opt_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
+                                  void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
+                                  void* stream);
+/* host only: (A_sub[I,I])^-1, row-major [(n_wp-2)^2] -- what the kernel's metric table holds */
+KINHIP_API int kin_traj_metric_inverse(int32_t n_wp, double* out);
 
 #ifdef __cplusplus
 }

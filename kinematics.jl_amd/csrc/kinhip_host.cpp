@@ -276,6 +276,10 @@ int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** 
         top->parts = std::move(parts);
     }
     top->n_sph = c->n_spheres;
+    for (int32_t k = 0; k < c->n_q; ++k) {  // (kin_traj_opt_batch clamps to these)
+        top->col_lo.push_back(m->jlo[c->q_joint_ids[k] - 1]);
+        top->col_hi.push_back(m->jhi[c->q_joint_ids[k] - 1]);
+    }
     *out = top.release();
     return KIN_OK;
 }

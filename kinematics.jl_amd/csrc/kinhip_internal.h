@@ -154,6 +154,24 @@ hipError_t launch_coll_scene(const KProg<T>& P, const KStep<T>* steps, const KSp
                              int64_t n, T* dists, int64_t ldd, T* grads, int64_t ldg, T* min_dist, const JitFns* jf,
                              const JitFns* jfs, hipStream_t st);
 
+// k_traj (kin_traj_opt_batch, kinhip_traj_dev.h): a lane keeps its waypoint's q columns (+ base) in registers,
+// kTrajNdSmall of them for chain bounds <= 8, kTrajNdLarge for 12 / 16; chains of 32 steps are refused
+constexpr int kTrajNdSmall = 12, kTrajNdLarge = 20, kTrajMaxChain = 16, kTrajMaxWp = 64;
+struct TrajArgs {
+    int32_t n_wp, max_iters;
+    double margin, band, weight, feas, ftol, max_step;
+};
+// per q column (unused columns: W = iW = 0, lo = -inf, hi = +inf)
+struct TrajDof {
+    double W[kTrajNdLarge], iW[kTrajNdLarge];  // dof_weights^2 and its reciprocal
+    double lo[kTrajNdLarge], hi[kTrajNdLarge];  // joint limits (base columns unbounded)
+};
+// minv: (A_sub[I,I])^-1 of n_wp waypoints on the device, row-major (symmetric, so also its transpose)
+template <typename T>
+hipError_t launch_traj(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
+                       const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minv,
+                       T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
+
 template <typename T>
 hipError_t launch_pose_residual(const T* poses, int64_t ldp, const T* target, int64_t ldt, int64_t n, int rows, T* vals,
                                 int64_t ldv, hipStream_t st);

@@ -200,7 +200,13 @@ struct kin_plan {
         const auto it = scene_jit.find(uid);
         return it == scene_jit.end() ? nullptr : jit_fns(it->second);
     }
+    // kin_traj_opt_batch: the q columns' joint limits (base columns unbounded; kin_coll_plan_create) and the
+    // metric tables (A_sub[I,I])^-1 on the device, in the plan's dtype, by n_wp (staged on first use)
+    std::vector<double> col_lo, col_hi;
+    mutable std::mutex traj_mu;
+    mutable std::map<int32_t, void*> traj_minv;
     ~kin_plan() {
+        for (auto& kv : traj_minv) (void)hipFree(kv.second);
         for (auto& kv : scene_jit) jit_destroy(kv.second);
         if (d_ikc) (void)hipFree(d_ikc);
         jit_destroy(jit);

@@ -1,0 +1,155 @@
+// kinhip_trajopt.cpp -- C-ABI of the batched trajectory optimiser: kin_traj_opt_batch (k_traj,
+// kinhip_traj.hip) and its metric table.
+//
+// Reference semantics restated here (host side):
+//   Objective's A_sub (finite-difference accelerations)    src/planning.jl:1-28
+//   the two end ConfigurationConstraints of a problem      src/planning.jl:310-330
+#include <cmath>
+#include <string>
+#include <vector>
+
+#include "kinhip_plan.h"
+
+namespace kinhip {
+namespace {
+
+// (A_sub[I,I])^-1 for n_wp waypoints, I the interior ones: Gauss-Jordan on the symmetric positive
+// definite pentadiagonal block (no pivoting needed), accumulated in long double
+void traj_metric_inverse(int n_wp, double* out) {
+    const int n = n_wp - 2;
+    std::vector<long double> A((size_t)n_wp * n_wp, 0.0L);
+    const long double blk[3] = {1.0L, -2.0L, 1.0L};
+    for (int i = 1; i < n_wp - 1; ++i)
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) A[(size_t)(i - 1 + r) * n_wp + (i - 1 + c)] += blk[r] * blk[c];
+    std::vector<long double> M((size_t)n * 2 * n, 0.0L);  // [A_II | 1]
+    for (int r = 0; r < n; ++r) {
+        for (int c = 0; c < n; ++c) M[(size_t)r * 2 * n + c] = A[(size_t)(r + 1) * n_wp + (c + 1)];
+        M[(size_t)r * 2 * n + n + r] = 1.0L;
+    }
+    for (int p = 0; p < n; ++p) {
+        const long double ip = 1.0L / M[(size_t)p * 2 * n + p];
+        for (int c = 0; c < 2 * n; ++c) M[(size_t)p * 2 * n + c] *= ip;
+        for (int r = 0; r < n; ++r) {
+            if (r == p) continue;
+            const long double fct = M[(size_t)r * 2 * n + p];
+            if (fct == 0.0L) continue;
+            for (int c = 0; c < 2 * n; ++c) M[(size_t)r * 2 * n + c] -= fct * M[(size_t)p * 2 * n + c];
+        }
+    }
+    for (int r = 0; r < n; ++r)
+        for (int c = 0; c < n; ++c)  // symmetrised: the kernel reads the table as its own transpose
+            out[(size_t)r * n + c] = (double)(0.5L * (M[(size_t)r * 2 * n + n + c] + M[(size_t)c * 2 * n + n + r]));
+}
+
+// the plan's device table for n_wp (dtype of the plan); the first call for an n_wp stages it (synchronous)
+int traj_metric_table(const kin_plan* p, int32_t n_wp, void* stream, const void** out) {
+    std::lock_guard<std::mutex> lk(p->traj_mu);
+    const auto it = p->traj_minv.find(n_wp);
+    if (it != p->traj_minv.end()) {
+        *out = it->second;
+        return KIN_OK;
+    }
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
+    if (cs == hipStreamCaptureStatusActive)
+        return set_error(KIN_E_INVALID, "kin_traj_opt_batch: the plan's first call for this n_wp stages its metric "
+                                        "table and cannot run inside a stream capture (make one call outside the "
+                                        "capture first)");
+    const size_t n = (size_t)(n_wp - 2) * (n_wp - 2);
+    std::vector<double> h(n ? n : 1);
+    traj_metric_inverse(n_wp, h.data());
+    std::vector<float> hf(h.begin(), h.end());
+    void* d = nullptr;
+    const bool f32 = p->dtype == KIN_F32;
+    const int rc = upload(&d, {{f32 ? (const void*)hf.data() : (const void*)h.data(), h.size() * (f32 ? 4 : 8), 0}},
+                          "kin_traj_opt_batch");
+    if (rc != KIN_OK) {
+        if (d) (void)hipFree(d);
+        return rc;
+    }
+    p->traj_minv.emplace(n_wp, d);
+    *out = d;
+    return KIN_OK;
+}
+
+}  // namespace
+}  // namespace kinhip
+
+extern "C" {
+
+int kin_traj_metric_inverse(int32_t n_wp, double* out) {
+    if (!out) return set_error(KIN_E_INVALID, "kin_traj_metric_inverse: null out");
+    if (n_wp < 3 || n_wp > kTrajMaxWp)
+        return set_error(KIN_E_UNSUPPORTED, "kin_traj_metric_inverse: n_wp must be in 3.." + std::to_string(kTrajMaxWp));
+    traj_metric_inverse(n_wp, out);
+    return KIN_OK;
+}
+
+int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
+                       int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    auto bad = [](int code, const std::string& w) { return set_error(code, "kin_traj_opt_batch: " + w); };
+    // the parameters first (they need no plan), then the plan and the union, then the arrays
+    if (!prm) return bad(KIN_E_INVALID, "null parameters");
+    if (prm->n_wp < 3 || prm->n_wp > kTrajMaxWp)
+        return bad(KIN_E_UNSUPPORTED, "n_wp must be in 3.." + std::to_string(kTrajMaxWp) + " (one lane per waypoint of a wave)");
+    if (prm->max_iters < 1) return bad(KIN_E_INVALID, "max_iters must be >= 1");
+    if (!(prm->weight > 0) || !std::isfinite(prm->weight)) return bad(KIN_E_INVALID, "weight must be finite and > 0");
+    if (!(prm->max_step > 0) || !std::isfinite(prm->max_step)) return bad(KIN_E_INVALID, "max_step must be finite and > 0");
+    if (!(prm->ftol > 0) || !std::isfinite(prm->ftol)) return bad(KIN_E_INVALID, "ftol must be finite and > 0");
+    if (!std::isfinite(prm->margin) || !(prm->band >= 0) || !std::isfinite(prm->band) || !(prm->feas >= 0) ||
+        !std::isfinite(prm->feas))
+        return bad(KIN_E_INVALID, "margin must be finite, band and feas finite and >= 0");
+    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
+    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
+    if (!p->parts.empty())
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off several chains (one sphere group only)");
+    if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
+    if (p->geom.maxA > kTrajMaxChain)
+        return bad(KIN_E_UNSUPPORTED, "the sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
+    const int nd_max = p->geom.maxA <= 8 ? kTrajNdSmall : kTrajNdLarge;
+    if (p->nqcols > nd_max)
+        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(nd_max) + " q columns (+ base) for this chain");
+    if ((int)p->col_lo.size() != p->n_q) return bad(KIN_E_INVALID, "plan without joint limits");
+    const double* dw = prm->dof_weights;
+    for (int k = 0; dw && k < p->nqcols; ++k)
+        if (!(dw[k] > 0) || !std::isfinite(dw[k])) return bad(KIN_E_INVALID, "dof_weights must be finite and > 0");
+    if (n_traj < 0) return bad(KIN_E_INVALID, "n_traj < 0");
+    if (n_traj == 0) return KIN_OK;
+    if (n_traj > (int64_t(1) << 40) / prm->n_wp) return bad(KIN_E_INVALID, "n_traj * n_wp too large");
+    const int64_t cols = n_traj * prm->n_wp;
+    if (!xi || ldx < cols) return bad(KIN_E_INVALID, "bad xi / ldx (ldx >= n_traj * n_wp)");
+    if (info && ldi < n_traj) return bad(KIN_E_INVALID, "ldi < n_traj");
+    if (const int rc = check_device(p->device, "kin_traj_opt_batch", "the plan")) return rc;
+    if (const int rc = check_device(sdf->device, "kin_traj_opt_batch", "the kin_sdf")) return rc;
+    const void* minv = nullptr;
+    if (const int rc = traj_metric_table(p, prm->n_wp, stream, &minv)) return rc;
+
+    TrajDof dof;
+    for (int k = 0; k < kTrajNdLarge; ++k) {
+        dof.W[k] = dof.iW[k] = 0.0;
+        dof.lo[k] = -INFINITY;
+        dof.hi[k] = INFINITY;
+    }
+    for (int k = 0; k < p->nqcols; ++k) {
+        const double w = dw ? dw[k] : 1.0;
+        dof.W[k] = w * w;
+        dof.iW[k] = 1.0 / (w * w);
+        if (k < p->n_q) {
+            dof.lo[k] = p->col_lo[k];
+            dof.hi[k] = p->col_hi[k];
+        }
+    }
+    const TrajArgs ta{prm->n_wp, prm->max_iters, prm->margin, prm->band, prm->weight, prm->feas, prm->ftol, prm->max_step};
+    const CollArgs ca{INFINITY, 0.0, sdf->n_boxes, sdf->n_aabb, 0, 0, {sdf->bc[0], sdf->bc[1], sdf->bc[2]},
+                      {sdf->bh[0], sdf->bh[1], sdf->bh[2]}};
+    const hipError_t e = by_dtype(p->dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_traj<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof,
+                              (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj launch: ") + hipGetErrorString(e));
+    return KIN_OK;
+}
+
+}  // extern "C"

@@ -680,6 +680,51 @@ function pose_const!(hm::HIPModel, link::Link, joints::Vector{<:Joint}, with_rot
     vals, jac
 end
 
+# --- batched trajectory optimisation: many plan_trajectory problems per launch (kin_traj_opt_batch) ---
+
+struct KinTrajParams
+    n_wp::Int32
+    max_iters::Int32
+    margin::Float64
+    band::Float64
+    weight::Float64
+    feas::Float64
+    ftol::Float64
+    max_step::Float64
+    dof_weights::Ptr{Float64}
+end
+
+"""`plan_trajectories!(hm, sscc, joints, sdf, Xi, n_wp; ...)`: optimise the n_traj = size(Xi, 1) / n_wp trajectories
+held in Xi (row t * n_wp + w + 1 = waypoint w of trajectory t, columns = dof; in: the initial guesses, e.g.
+straight lines; out: the results, the end waypoints untouched) in one launch: the smoothness objective of
+src/planning.jl:1-28 plus one-sided sphere-clearance penalties, by the covariant projected gradient of
+include/kinhip.h (a solver of this engine's own, not the reference's SLSQP).  Returns (Xi, iters, info):
+iters[t] <= max_iters when trajectory t ended feasible; info (n_traj, 4) = merit, smoothness term, minimum
+interior sphere distance, accepted steps.  The first call for a new n_wp stages a small table (synchronous)."""
+function plan_trajectories!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionChecker, joints::Vector{<:Joint},
+                            sdf::HIPSDF, Xi::ROCMatrix{T}, n_wp::Integer; margin::Real=2e-2, band::Real=3e-2,
+                            weight::Real=10.0, feas::Real=1e-3, ftol::Real=1e-6, max_step::Real=0.5,
+                            max_iters::Integer=200, dof_weights::Union{Nothing,Vector{Float64}}=nothing) where {T}
+    N = size(Xi, 1)
+    N % n_wp == 0 || error("size(Xi, 1) must be a multiple of n_wp")
+    n_traj = div(N, n_wp)
+    p = coll_plan!(hm, T, sscc, joints)
+    iters = ROCVector{Int32}(undef, n_traj)
+    info = ROCMatrix{T}(undef, n_traj, 4)
+    dw = dof_weights === nothing ? Float64[] : dof_weights
+    GC.@preserve dw begin
+        prm = Ref(KinTrajParams(Int32(n_wp), Int32(max_iters), Float64(margin), Float64(band), Float64(weight),
+                                Float64(feas), Float64(ftol), Float64(max_step),
+                                dof_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(dw)))
+        check(ccall((:kin_traj_opt_batch, libkinhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{KinTrajParams}, Ptr{T}, Int64, Int64, Ptr{Int32}, Ptr{T}, Int64,
+                     Ptr{Cvoid}),
+                    p, sdf.handle, prm, pointer(Xi), stride(Xi, 2), n_traj, pointer(iters), pointer(info), n_traj,
+                    stream_ptr()))
+    end
+    Xi, iters, info
+end
+
 # --- the reference's plan_trajectory with the collision queries on the GPU (src/planning.jl:32-68, 332-401) ---
 
 const HIP_MODELS = WeakKeyDict{Mechanism,HIPModel}()

@@ -25,7 +25,8 @@ from .collision import (  # noqa: F401
 )
 from .planning import (  # noqa: F401
     ConfigurationConstraint, EqConst, IneqConst, Objective, PoseConstraint, construct_problem,
-    collision_aware_ik, create_straight_trajectory, plan_trajectory,
+    collision_aware_ik, create_straight_trajectory, plan_trajectories, plan_trajectory, traj_metric_inverse,
+    traj_opt_batch,
 )
 
 FETCH_ARM_JOINTS = [

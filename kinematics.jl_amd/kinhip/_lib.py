@@ -42,6 +42,7 @@ EXPORTS = [
     "kin_ineq_const_batch", "kin_pose_const_batch",
     "kin_coll_ik_plan_create", "kin_ik_coll_batch", "kin_ik_coll_batch_scene", "kin_sdf_create_attached",
     "kin_coll_batch_scene", "kin_plan_ik_sched_stats", "kin_plan_specialize_scene", "kin_ik_coll_batch_alt",
+    "kin_traj_opt_batch", "kin_traj_metric_inverse",
 ]
 
 
@@ -87,6 +88,12 @@ class IkSchedStats(C.Structure):
 
 class IkCollParams(C.Structure):
     _fields_ = [("margin", C.c_double), ("band", C.c_double), ("weight", C.c_double), ("feas", C.c_double)]
+
+
+class TrajParams(C.Structure):
+    _fields_ = [("n_wp", C.c_int32), ("max_iters", C.c_int32), ("margin", C.c_double), ("band", C.c_double),
+                ("weight", C.c_double), ("feas", C.c_double), ("ftol", C.c_double), ("max_step", C.c_double),
+                ("dof_weights", C.c_void_p)]
 
 
 _lib = None
@@ -149,6 +156,8 @@ def lib():
         "kin_ik_coll_batch_alt": ([P, P, P, P, P, I64, P, I64, P, P, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_plan_ik_sched_stats": ([P, P], C.c_int),
         "kin_plan_specialize_scene": ([P, P], C.c_int),
+        "kin_traj_opt_batch": ([P, P, P, P, I64, I64, P, P, I64, P], C.c_int),
+        "kin_traj_metric_inverse": ([I32, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
     # for builds of older sources that lack newer entry points

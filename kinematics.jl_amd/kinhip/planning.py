@@ -17,6 +17,11 @@ path).  NLopt and Ipopt are not installed, so ``solver=:NLOPT`` / ``:IPOPT`` are
 refused; ``solver="SLSQP_BOUNDED"`` (the default) is SciPy's SLSQP with the
 joint-limit bounds the reference's NLopt path sets (src/planning.jl:364-369) --
 SciPy's implementation, not NLopt's -- and reports its status as a symbol.
+
+``plan_trajectories`` / ``plan_trajectory(..., solver="GPU")`` are the batched, device-resident
+alternative: ``kin_traj_opt_batch`` runs the whole descent of many trajectories in one kernel (a
+covariant projected gradient on the smoothness objective plus sphere-clearance penalties -- a
+different solver from SLSQP, see include/kinhip.h).
 """
 from __future__ import annotations
 
@@ -207,17 +212,110 @@ def construct_problem(sscc, joints, sdf, q_start, q_goal, n_wp, n_dof, margin, p
             n_dof * n_wp)
 
 
+def traj_metric_inverse(n_wp: int) -> np.ndarray:
+    """kin_traj_metric_inverse: (A_sub[I,I])^-1 over the interior waypoints, [(n_wp-2), (n_wp-2)] (host)."""
+    out = np.zeros((max(int(n_wp) - 2, 0), max(int(n_wp) - 2, 0)))
+    K.check(K.lib().kin_traj_metric_inverse(int(n_wp), out.ctypes.data if out.size else None))
+    return out
+
+
+def traj_opt_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=2e-2, band=3e-2, weight=10.0, feas=1e-3,
+                   ftol=1e-6, max_step=0.5, max_iters=200, dof_weights=None, iters=None, info=None, stream=None):
+    """kin_traj_opt_batch in place on X [n_dof, n_traj * n_wp] (column t * n_wp + w = waypoint w of trajectory t;
+    the end columns of every trajectory stay as given) with a ``CollisionPlan`` -> (iters [n_traj] int32,
+    info [4, n_traj]: merit, smoothness term, min interior sphere distance, accepted steps).  Async on the stream
+    after the plan's first call for this n_wp (which stages the metric table)."""
+    if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
+            or X.shape[1] % int(n_wp) != 0):
+        raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
+    n_traj = X.shape[1] // int(n_wp)
+    dev = X.device
+    it = iters if iters is not None else torch.empty(n_traj, dtype=torch.int32, device=dev)
+    nf = info if info is not None else torch.empty((4, n_traj), dtype=plan.dtype, device=dev)
+    dw = None if dof_weights is None else np.ascontiguousarray(np.asarray(dof_weights, np.float64))
+    if dw is not None and dw.shape != (plan.n_dof,):
+        raise ValueError(f"dof_weights must have {plan.n_dof} entries")
+    prm = K.TrajParams(int(n_wp), int(max_iters), float(margin), float(band), float(weight), float(feas), float(ftol),
+                       float(max_step), dw.ctypes.data if dw is not None else None)
+    st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+    K.check(K.lib().kin_traj_opt_batch(plan._h, sdf._h, C.byref(prm), X.data_ptr(), X.stride(0), n_traj,
+                                       it.data_ptr(), nf.data_ptr(), nf.stride(0), st))
+    return it, nf
+
+
+def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, Q_start, Q_goal, n_wp: int,
+                      margin=2e-2, band=3e-2, weight=10.0, max_iters=200, dtype=torch.float64, X0=None, stream=None,
+                      feas=1e-3, ftol=1e-6, max_step=0.5, dof_weights=None, plan=None, check_ends=True):
+    """Many ``plan_trajectory`` problems in one launch (kin_traj_opt_batch): Q_start / Q_goal [n_dof, n_traj]
+    (or one [n_dof] vector for every trajectory) -> (X [n_dof, n_traj * n_wp], iters [n_traj], info [4, n_traj]).
+    Trajectory t is X[:, t * n_wp:(t + 1) * n_wp]; it is feasible (every interior sphere distance >= margin -
+    feas, merit settled to ftol) when iters[t] <= max_iters.  The straight-line initial guesses
+    (create_straight_trajectory) are built on the device unless X0 is given; `check_ends` evaluates every start
+    and goal in one kin_coll_batch and raises if one is in collision, as the reference asserts (it reads one
+    flag back: pass False to stay asynchronous).  `plan`: a ``CollisionPlan`` of (sscc, joints, dtype) to reuse
+    (its metric table is staged once per n_wp)."""
+    n_wp = int(n_wp)
+    dev = _device()
+    plan = plan if plan is not None else sscc.plan(list(joints), dtype=dtype)
+    if plan.dtype != dtype:
+        raise ValueError("plan dtype differs from dtype")
+    n_dof = plan.n_dof
+
+    def as_cols(Q, other):
+        Q = torch.as_tensor(Q, dtype=dtype).to(dev)
+        if Q.dim() == 1:
+            n = other.shape[1] if isinstance(other, torch.Tensor) and other.dim() == 2 else 1
+            Q = Q.reshape(-1, 1).expand(-1, n)
+        if Q.dim() != 2 or Q.shape[0] != n_dof:
+            raise ValueError(f"Q_start / Q_goal must be ({n_dof},) or ({n_dof}, n_traj)")
+        return Q.contiguous()
+
+    Qs = as_cols(Q_start, Q_goal if isinstance(Q_goal, torch.Tensor) else torch.as_tensor(Q_goal))
+    Qg = as_cols(Q_goal, Qs)
+    if Qs.shape[1] == 1 and Qg.shape[1] > 1:
+        Qs = Qs.expand(-1, Qg.shape[1]).contiguous()
+    if Qs.shape != Qg.shape:
+        raise ValueError("Q_start and Q_goal differ in shape")
+    n_traj = Qs.shape[1]
+    st = stream or torch.cuda.current_stream(dev)
+    with torch.cuda.stream(st):
+        if check_ends:
+            _, _, mn = plan.run(sdf, torch.cat([Qs, Qg], 1), dists=False, min_dist=True, stream=st)
+            if not bool((mn > 0).all()):
+                raise AssertionError("start / goal in collision")
+        if X0 is None:
+            # create_straight_trajectory (src/planning.jl:304-308) per trajectory; the last waypoint is the goal itself
+            step = (Qg - Qs) / (n_wp - 1)
+            i = torch.arange(n_wp, dtype=dtype, device=dev)
+            X = (Qs[:, :, None] + step[:, :, None] * i[None, None, :])
+            X[:, :, n_wp - 1] = Qg
+            X = X.reshape(n_dof, n_traj * n_wp).contiguous()
+        else:
+            X = torch.as_tensor(X0, dtype=dtype).to(dev).reshape(n_dof, n_traj * n_wp).clone()
+        it, nf = traj_opt_batch(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
+                                max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
+    return X, it, nf
+
+
 def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_start, q_goal, n_wp: int,
                     margin=2e-2, partial_consts=(), ftol_abs=1e-3, solver="SLSQP_BOUNDED", maxiter=200):
     """src/planning.jl:332-401 -> (q_seq [n_dof, n_wp], status).  Constraint evaluations on the GPU.
 
     ``solver``: "SLSQP_BOUNDED" (SciPy SLSQP + joint-limit bounds; status ``:SUCCESS`` /
     ``:MAXEVAL_REACHED`` / ``:FAILURE``) or "SCIPY" (the reference's :SCIPY path: no bounds, returns
-    SciPy's result).  "NLOPT" and "IPOPT" raise: those libraries are not installed."""
+    SciPy's result).  "NLOPT" and "IPOPT" raise: those libraries are not installed.  "GPU": the batched
+    penalty descent of ``plan_trajectories`` on a batch of one (fp64; no partial constraints; status
+    ``:SUCCESS`` when it ended feasible, else ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used)."""
     from scipy.optimize import minimize
     from .collision import compute_coll_dists
 
     solver = str(solver).lstrip(":").upper()
+    if solver == "GPU":
+        if len(partial_consts):
+            raise ValueError("solver 'GPU' takes no partial constraints")
+        X, it, _ = plan_trajectories(sscc, joints, sdf, np.asarray(q_start, np.float64), np.asarray(q_goal, np.float64),
+                                     n_wp, margin=margin, max_iters=maxiter, dtype=torch.float64)
+        return X.cpu().numpy(), (":SUCCESS" if int(it[0]) <= maxiter else ":MAXEVAL_REACHED")
     if solver in ("NLOPT", "IPOPT"):
         raise ValueError(f"solver :{solver} needs a library that is not installed; use 'SLSQP_BOUNDED' "
                          "(SciPy SLSQP with the joint-limit bounds) or 'SCIPY'")

@@ -54,7 +54,7 @@ def scan(co):
 
 def main(argv):
     obj_dir = os.path.join(ROOT, "kinematics.jl_amd", "lib", "obj")
-    objs = [os.path.join(obj_dir, f"kinhip_{k}.o") for k in ("fk", "ik", "ikt", "coll")]  # (the product's)
+    objs = [os.path.join(obj_dir, f"kinhip_{k}.o") for k in ("fk", "ik", "ikt", "coll", "traj")]  # (the product's)
     objs = [o for o in objs if os.path.exists(o)]  # (lib/obj stays in the build container: not on a GPU box)
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:

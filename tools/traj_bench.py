@@ -1,0 +1,139 @@
+"""Throughput of the batched trajectory optimiser (kin_traj_opt_batch, kinhip.plan_trajectories) on the reference's
+planning scene (test/test_planning.jl: Fetch, four collision links, a thin box; q_start = 0, 32 collision-free IK
+goals for (0.3, -0.4, 1.2)), n_wp = 10, fp32 and fp64, the 32 problems replicated to 32 / 1,024 / 32,768
+trajectories.  For comparison: the only way to do the same work before, kinhip.plan_trajectory (SciPy SLSQP on
+the host, one GPU constraint evaluation per iterate) looped over the same 32 problems.  The two solvers differ
+(a penalty descent vs SLSQP on the constrained problem): the comparison is on feasibility and time, not iterates.
+
+    python tools/traj_bench.py [--reps 5] [--no-slsqp] [--out profiles/traj_bench.json]
+
+Timing: a host clock around calls that end in a device synchronise, after a warm-up call per shape; the median of
+--reps repeats and their min / max.  Iterations per second counts, per trajectory, the iterations the kernel ran
+(iters, or max_iters when a trajectory did not finish; an upper bound for stalled ones); for SLSQP it is the
+constraint evaluations per second (one per iterate or line-search point).  Needs a GPU: there is no CPU fallback."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (os.path.join(ROOT, "kinematics.jl_amd"), os.path.join(ROOT, "oracle")):
+    sys.path.insert(0, p)
+
+import kinhip  # noqa: E402
+
+COLL_LINKS = ["wrist_flex_link", "torso_lift_link", "upperarm_roll_link", "elbow_flex_link"]
+N_WP, MARGIN, FEAS, MAX_ITERS = 10, 0.02, 1e-3, 200
+
+
+def scene():
+    m = kinhip.parse_urdf(os.path.join(ROOT, "tests", "golden", "fetch.urdf"))
+    joints = [m.find_joint(n) for n in kinhip.FETCH_ARM_JOINTS]
+    sscc = kinhip.SweptSphereCollisionChecker(m)
+    for n in COLL_LINKS:
+        kinhip.add_coll_links(sscc, m.find_link(n))
+    T = np.eye(4)
+    T[:3, 3] = (0.4, -0.25, 0.7)
+    sdf = kinhip.UnionSDF([kinhip.BoxSDF(T, (0.05, 0.05, 0.5))])
+    return m, joints, sscc, sdf
+
+
+def goals(m, joints, sscc, sdf, n=32):
+    """The first n collision-free (min d > 0.05) batched-IK solutions from default_rng(0).uniform(-1, 1) starts."""
+    gl = m.find_link("gripper_link")
+    N = 512
+    Q0 = torch.tensor(np.random.default_rng(0).uniform(-1, 1, (8, N)), dtype=torch.float64, device="cuda")
+    tgt = torch.tensor(np.repeat(np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0.3, -0.4, 1.2]).reshape(12, 1), N, axis=1),
+                       dtype=torch.float64, device="cuda")
+    plan = m.plan(joints, out_links=[gl], jac_link=gl, jac_joints=joints, dtype=torch.float64)
+    Q, it, _ = plan.ik_dls(tgt, Q0, with_rot=False, max_iters=64)
+    _, _, mn = sscc.plan(joints, dtype=torch.float64).run(sdf, Q, dists=False, min_dist=True)
+    ok = ((it <= 64) & (mn > 0.05)).nonzero()[:n, 0]
+    assert ok.numel() == n
+    return Q[:, ok].contiguous()
+
+
+def interior_clearance(cp64, sdf, X, n_traj):
+    _, _, mn = cp64.run(sdf, X.double(), dists=False, min_dist=True)
+    return mn.reshape(n_traj, N_WP)[:, 1:-1].min(1).values
+
+
+def timed(fn, reps):
+    fn()  # warm-up: code objects, the metric table, allocator
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append(time.perf_counter() - t0)
+    return float(np.median(ts)), float(min(ts)), float(max(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--no-slsqp", action="store_true")
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("traj_bench.py needs a GPU")
+    m, joints, sscc, sdf = scene()
+    G = goals(m, joints, sscc, sdf)
+    q_start = np.zeros(8)
+    cp64 = sscc.plan(joints, dtype=torch.float64)
+    res = {"scene": "fetch + thin box, 32 IK goals", "n_wp": N_WP, "max_iters": MAX_ITERS, "gpu": []}
+    for dtype in (torch.float32, torch.float64):
+        cp = sscc.plan(joints, dtype=dtype)
+        for n_traj in (32, 1024, 32768):
+            Qg = G.repeat(1, n_traj // 32).to(dtype).contiguous()
+            out = {}
+
+            def call():
+                out["r"] = kinhip.plan_trajectories(sscc, joints, sdf, q_start, Qg, N_WP, margin=MARGIN, feas=FEAS,
+                                                    max_iters=MAX_ITERS, dtype=dtype, plan=cp, check_ends=False)
+            med, lo, hi = timed(call, a.reps)
+            X, it, info = out["r"]
+            ran = torch.clamp(it, max=MAX_ITERS).sum().item()
+            d = interior_clearance(cp64, sdf, X, n_traj)
+            feas32 = int((d[:32] >= MARGIN - FEAS - (1e-6 if dtype == torch.float32 else 0.0)).sum())
+            row = {"dtype": str(dtype).split(".")[-1], "n_traj": n_traj, "seconds_median": med, "seconds_min": lo,
+                   "seconds_max": hi, "traj_per_s": n_traj / med, "iters_per_s": ran / med,
+                   "mean_iters": ran / n_traj, "feasible_of_32": feas32, "done_of_32": int((it[:32] <= MAX_ITERS).sum())}
+            res["gpu"].append(row)
+            print(json.dumps(row), flush=True)
+    if not a.no_slsqp:
+        # the previous path: one host SLSQP per problem (its own GPU launch and copy per iterate)
+        from kinhip import planning
+        evals = [0]
+        inner = planning.IneqConst.__call__
+
+        def counted(self, xi, val_vec, jac_mat):  # one GPU constraint evaluation per SLSQP iterate / line-search point
+            evals[0] += 1
+            return inner(self, xi, val_vec, jac_mat)
+        planning.IneqConst.__call__ = counted
+        Gh = G.cpu().numpy()
+        t0 = time.perf_counter()
+        feas, ok = 0, 0
+        for t in range(32):
+            q_seq, status = kinhip.plan_trajectory(sscc, joints, sdf, q_start, Gh[:, t], N_WP, margin=MARGIN,
+                                                   ftol_abs=1e-5)
+            X = torch.tensor(np.ascontiguousarray(q_seq), dtype=torch.float64, device="cuda")
+            feas += int(interior_clearance(cp64, sdf, X, 1)[0] >= MARGIN - FEAS)
+            ok += int(status == ":SUCCESS")
+        dt = time.perf_counter() - t0
+        planning.IneqConst.__call__ = inner
+        res["slsqp"] = {"n_traj": 32, "seconds": dt, "traj_per_s": 32 / dt, "constraint_evals_per_s": evals[0] / dt,
+                        "mean_constraint_evals": evals[0] / 32, "feasible_of_32": feas, "success_of_32": ok}
+        print(json.dumps(res["slsqp"]), flush=True)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
