@@ -169,6 +169,9 @@ KINHIP_API int kin_plan_create(const kin_model* m, const kin_plan_desc* desc, ki
 KINHIP_API int kin_plan_destroy(kin_plan* p);
 /* Number of batch columns q must hold, Jacobian rows and columns. */
 KINHIP_API int kin_plan_shape(const kin_plan* p, int32_t* n_qcols, int32_t* jac_rows, int32_t* jac_cols);
+/* Diagnostic: the chain bound the plan was staged with (the padded step count of its
+ * longest chain, which the launchers pick their kernel instantiation by). */
+KINHIP_API int kin_plan_chain_bound(const kin_plan* p, int32_t* out);
 
 /* Batched get_transform (+ get_jacobian!) for N configurations:
  * src/algorithm.jl:1-21 and :83-106 with set_joint_angles per config.

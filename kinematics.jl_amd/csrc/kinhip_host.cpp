@@ -84,6 +84,12 @@ int kin_plan_shape(const kin_plan* p, int32_t* nq, int32_t* rows, int32_t* cols)
     return KIN_OK;
 }
 
+int kin_plan_chain_bound(const kin_plan* p, int32_t* out) {
+    if (!p || !out) return set_error(KIN_E_INVALID, "kin_plan_chain_bound: null plan / out");
+    *out = p->geom.maxA;
+    return KIN_OK;
+}
+
 namespace {
 int plan_run(const kin_plan* p, const void* q, int64_t ldq, int64_t n, void* poses, int64_t ldp, void* jac,
              int64_t ldj, const TileArgs& ta, void* stream, const char* fn) {

@@ -42,7 +42,7 @@ EXPORTS = [
     "kin_ineq_const_batch", "kin_pose_const_batch",
     "kin_coll_ik_plan_create", "kin_ik_coll_batch", "kin_ik_coll_batch_scene", "kin_sdf_create_attached",
     "kin_coll_batch_scene", "kin_plan_ik_sched_stats", "kin_plan_specialize_scene", "kin_ik_coll_batch_alt",
-    "kin_traj_opt_batch", "kin_traj_metric_inverse",
+    "kin_traj_opt_batch", "kin_traj_metric_inverse", "kin_plan_chain_bound",
 ]
 
 
@@ -158,6 +158,7 @@ def lib():
         "kin_plan_specialize_scene": ([P, P], C.c_int),
         "kin_traj_opt_batch": ([P, P, P, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_traj_metric_inverse": ([I32, P], C.c_int),
+        "kin_plan_chain_bound": ([P, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
     # for builds of older sources that lack newer entry points

@@ -165,6 +165,13 @@ class CollisionPlan:
         K.check(K.lib().kin_plan_specialized(self._h, C.byref(v)))
         return v.value
 
+    @property
+    def chain_bound(self) -> int:
+        """kin_plan_chain_bound: the chain bound the plan was staged with (diagnostic)."""
+        v = C.c_int32()
+        K.check(K.lib().kin_plan_chain_bound(self._h, C.byref(v)))
+        return v.value
+
     def run(self, sdf: UnionSDF, Q: torch.Tensor, dists=True, grads=False, min_dist=False,
             truncation=float("inf"), stream=None, scene_q: Optional[torch.Tensor] = None):
         """-> (dists [n_sph, N] | None, grads [n_sph, n_dof, N] | None, min_dist [N] | None). Async.

@@ -266,6 +266,13 @@ class Plan:
         K.check(K.lib().kin_plan_specialized(self._h, C.byref(v)))
         return v.value
 
+    @property
+    def chain_bound(self) -> int:
+        """kin_plan_chain_bound: the chain bound the plan was staged with (diagnostic)."""
+        v = C.c_int32()
+        K.check(K.lib().kin_plan_chain_bound(self._h, C.byref(v)))
+        return v.value
+
     def ik_sched_stats(self) -> dict:
         """kin_plan_ik_sched_stats: counters of the two-phase IK scratch-set scheduling (tests)."""
         st = K.IkSchedStats()

@@ -3,8 +3,9 @@ and the reference's planning scene (test/test_planning.jl) it is exercised on.
 
 Sphere centres and 3 x n Jacobians come from the oracle (OracleMech.fk_batch / fk_jac_batch); the box SDF and its
 analytic gradient are written here to the conventions of the kernel's box_gradient (the oracle's coll_batch takes a
-forward difference, ~1e-5 away, which would break iterate parity).  Not a test module: imported by
-tests/test_trajopt.py and tests/test_gpu_trajopt.py, which share the runs cached here."""
+forward difference, ~1e-5 away, which would break iterate parity).  ChainScene is the same for any robot (the
+random chains of tests/trajopt_cases.py).  Not a test module: imported by tests/test_trajopt.py and
+tests/test_gpu_trajopt.py, which share the runs cached here."""
 import functools
 
 import numpy as np
@@ -54,7 +55,42 @@ def union_box_sdf(p, poses, widths):
     return best, grad
 
 
-class Scene:
+class SceneBase:
+    """What merit() and run() use of a scene: om, ids, sph, rad, lo, hi, n_dof, box_poses, box_widths."""
+
+    def distances(self, Q):
+        """Q [n_dof, N] -> sphere distances [n_sph, N] and the SDF gradients at the centres [n_sph, N, 3]."""
+        N = Q.shape[1]
+        poses = self.om.fk_batch(Q, self.ids, self.sph)          # [n_sph, 12, N]
+        C = np.transpose(poses[:, 9:12, :], (0, 2, 1)).reshape(-1, 3)
+        d, g = union_box_sdf(C, self.box_poses, self.box_widths)
+        return d.reshape(len(self.sph), N) - self.rad[:, None], g.reshape(len(self.sph), N, 3)
+
+
+class ChainScene(SceneBase):
+    """Any robot: a UrdfTree, the batch joint ids in column order (off-chain joints allowed: their Jacobian columns
+    are zero), held joints at fixed angles, (link id, centre, radius) spheres and a union of boxes (4x4 poses, full
+    widths).  Unbounded joints and the base columns have +-inf limits, as the library's col_lo / col_hi."""
+
+    def __init__(self, tree, with_base, ids, held=(), held_ang=(), spheres=(), box_poses=(), box_widths=()):
+        self.with_base = bool(with_base)
+        self.tree = tree
+        self.om = O.OracleMech(tree, with_base=with_base)
+        if len(held):
+            self.om.set_joint_angles(list(held), np.concatenate([np.asarray(held_ang, np.float64),
+                                                                 np.zeros(3 if with_base else 0)]))
+        self.sph = [self.om.add_new_link(int(l), _T(c)) for l, c, _ in spheres]
+        self.rad = np.array([r for _, _, r in spheres], np.float64)
+        self.ids = [int(j) for j in ids]
+        nb = 3 if with_base else 0
+        self.n_dof = len(self.ids) + nb
+        self.lo = np.array([tree.joint_lower[j - 1] for j in self.ids] + [-np.inf] * nb, np.float64)
+        self.hi = np.array([tree.joint_upper[j - 1] for j in self.ids] + [np.inf] * nb, np.float64)
+        self.box_poses = [np.asarray(p, np.float64) for p in box_poses]
+        self.box_widths = [tuple(w) for w in box_widths]
+
+
+class Scene(SceneBase):
     """Fetch, the four collision links' spheres and the thin box, on the oracle."""
 
     def __init__(self, with_base):
@@ -73,14 +109,6 @@ class Scene:
         self.lo = np.array([self.tree.joint_lower[j - 1] for j in self.ids] + [-np.inf] * (self.n_dof - len(self.ids)))
         self.hi = np.array([self.tree.joint_upper[j - 1] for j in self.ids] + [np.inf] * (self.n_dof - len(self.ids)))
         self.box_poses, self.box_widths = [_T(BOX_POSE)], [BOX_WIDTH]
-
-    def distances(self, Q):
-        """Q [n_dof, N] -> sphere distances [n_sph, N] and the SDF gradients at the centres [n_sph, N, 3]."""
-        N = Q.shape[1]
-        poses = self.om.fk_batch(Q, self.ids, self.sph)          # [n_sph, 12, N]
-        C = np.transpose(poses[:, 9:12, :], (0, 2, 1)).reshape(-1, 3)
-        d, g = union_box_sdf(C, self.box_poses, self.box_widths)
-        return d.reshape(len(self.sph), N) - self.rad[:, None], g.reshape(len(self.sph), N, 3)
 
     def goals(self):
         """q_start = 0 and the first 32 collision-free (min d > 0.05) IK solutions for TARGET from
