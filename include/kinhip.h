@@ -543,6 +543,43 @@ KINHIP_API int kin_traj_opt_batch(const kin_plan* coll_plan, const kin_sdf* sdf,
 /* host only: (A_sub[I,I])^-1, row-major [(n_wp-2)^2] -- what the kernel's metric table holds */
 KINHIP_API int kin_traj_metric_inverse(int32_t n_wp, double* out);
 
+/* Pose constraints at a waypoint (the reference's PoseConstraint among plan_trajectory's partial_consts,
+ * src/planning.jl:90-138, 332-357) on the batched path.
+ *
+ * kin_traj_plan_create: kin_coll_plan_create plus the frames of 1..2 pose links for kin_traj_opt_pose_batch.  The
+ * plan is a collision plan: every kin_coll_* call, kin_ineq_const_batch and kin_traj_opt_batch accept it, with the
+ * results of a kin_coll_plan_create plan of the same desc (same sphere table).  The staged chain reaches the
+ * deepest of the spheres and the pose links; a pose link must lie on the sphere chain or its extension (fixed
+ * joints and joints held at the model's angles below a chain frame included), a link on another branch is
+ * KIN_E_UNSUPPORTED, as are more than 2 links and a chain of more than 8 steps after the extension. */
+KINHIP_API int kin_traj_plan_create(const kin_model* m, const kin_coll_desc* desc, int32_t n_pose_links,
+                                    const int32_t* pose_link_ids, kin_plan** out);
+typedef struct kin_traj_pose_params {
+    int32_t n_con;             /* 1 (more: KIN_E_UNSUPPORTED in this version) */
+    const int32_t* wp;         /* [n_con] 0-based interior waypoint, 1 .. n_wp-2 */
+    const int32_t* with_rot;   /* [n_con] 0: position, 3 rows; 1: position + orientation, 6 rows */
+    double weight, damp, tol_pos, tol_rot;
+} kin_traj_pose_params;
+/* kin_traj_opt_batch with pose link i of the plan held at a per-trajectory target at waypoint wp[i] (one
+ * constraint in this version).  Residual r = [p - p*; -log(R* R^T)] (the world axis-angle vector, as
+ * kin_ik_dls_batch with with_rot = 1), its derivative the geometric Jacobian J.  Merit: kin_traj_opt_batch's plus
+ * weight (|r_p| + |r_rot|), an exact penalty on the norms.  Step: with raw = kin_traj_opt_batch's covariant step,
+ * m = column wp-1 of (A[I,I])^-1 and S = J W^-1 J^T + damp I at the accepted state,
+ *     v = S^-1 (-r - J raw_wp),  u = W^-1 J^T v,  step_w = raw_w + (m[w-1] / m[wp-1]) u     (every interior w)
+ * -- CHOMP's constrained update: the gradient step projected onto the tangent of the linearised constraint in the
+ * metric plus one Newton correction spread over the trajectory by the metric's column -- then scaled and clamped as
+ * before.  Accept / reject, alpha and the stall rule as kin_traj_opt_batch on this merit; done additionally needs
+ * |r_p| < tol_pos and |r_rot| < tol_rot.  Pinned against tests/trajopt_pose_ref.py.
+ *   targets [12 * n_con][ldt]  3x4 column-major target poses, one column per trajectory
+ *   info    [6][ldi]           rows 0-3 as kin_traj_opt_batch, 4: |r_p|, 5: |r_rot| of the returned state (0 for
+ *                              position only); or NULL
+ * Limits (KIN_E_UNSUPPORTED): those of kin_traj_opt_batch; a plan of kin_traj_plan_create (with pose links) whose
+ * chain has at most 8 steps; n_con = 1.  Capture and the metric table as kin_traj_opt_batch (the same table). */
+KINHIP_API int kin_traj_opt_pose_batch(const kin_plan* traj_plan, const kin_sdf* sdf, const kin_traj_params* prm,
+                                       const kin_traj_pose_params* pose, const void* targets, int64_t ldt, void* xi,
+                                       int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
+                                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -215,31 +215,40 @@ int kin_plan_specialized(const kin_plan* p, uint32_t* kernels) {
     return KIN_OK;
 }
 
-int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** out) {
-    if (!m || !c || !out) return set_error(KIN_E_INVALID, "kin_coll_plan_create: null argument");
+namespace {
+// kin_coll_plan_create, and with pose links kin_traj_plan_create (fn names the entry point in the messages)
+int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose, const int32_t* pose_ids, kin_plan** out,
+                     const std::string& fn) {
+    if (!m || !c || !out) return set_error(KIN_E_INVALID, fn + ": null argument");
     if (c->n_spheres < 1 || !c->sphere_link_ids || !c->radii)
-        return set_error(KIN_E_INVALID, "kin_coll_plan_create: need >= 1 sphere with link ids and radii");
-    if (c->n_q < 0 || (c->n_q && !c->q_joint_ids)) return set_error(KIN_E_INVALID, "kin_coll_plan_create: bad q");
+        return set_error(KIN_E_INVALID, fn + ": need >= 1 sphere with link ids and radii");
+    if (c->n_q < 0 || (c->n_q && !c->q_joint_ids)) return set_error(KIN_E_INVALID, fn + ": bad q");
     const int32_t L = m->n_links, J = m->n_joints();
     std::vector<char> moving(J, 0);
     for (int32_t k = 0; k < c->n_q; ++k) {
         const int32_t j = c->q_joint_ids[k] - 1;
-        if (j < 0 || j >= J) return set_error(KIN_E_KEY, "kin_coll_plan_create: q joint id out of range");
+        if (j < 0 || j >= J) return set_error(KIN_E_KEY, fn + ": q joint id out of range");
         moving[j] = m->jtype[j] != KIN_JOINT_FIXED;
     }
     // Group the spheres by chain: the spine of a group is the remaining sphere anchor (nearest link
     // below a moving joint) with the most moving joints above it; the group takes every remaining
     // sphere whose anchor lies on the spine's root path.  One staged program per group.
+    const auto anchor_of = [&](int32_t x) {
+        while (x >= 0 && m->link_pjoint[x] >= 0 && !moving[m->link_pjoint[x]]) x = m->plink(x);
+        return x;
+    };
     std::vector<int32_t> anchor(c->n_spheres), depth(c->n_spheres);
     for (int32_t k = 0; k < c->n_spheres; ++k) {
         int32_t x = c->sphere_link_ids[k] - 1;
-        if (x < 0 || x >= L) return set_error(KIN_E_KEY, "kin_coll_plan_create: sphere link id out of range");
-        while (x >= 0 && m->link_pjoint[x] >= 0 && !moving[m->link_pjoint[x]]) x = m->plink(x);
+        if (x < 0 || x >= L) return set_error(KIN_E_KEY, fn + ": sphere link id out of range");
+        x = anchor_of(x);
         int dd = 0;
         for (int32_t y = x; y >= 0 && m->link_pjoint[y] >= 0; y = m->plink(y)) dd += moving[m->link_pjoint[y]];
         anchor[k] = x;
         depth[k] = dd;
     }
+    for (int32_t k = 0; k < n_pose; ++k)
+        if (pose_ids[k] < 1 || pose_ids[k] > L) return set_error(KIN_E_KEY, fn + ": pose link id out of range");
     std::vector<char> done(c->n_spheres, 0);
     std::vector<std::unique_ptr<kin_plan>> parts;
     int32_t left = c->n_spheres;
@@ -247,6 +256,17 @@ int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** 
         int32_t spine = -1, best = -1;
         for (int32_t k = 0; k < c->n_spheres; ++k)
             if (!done[k] && depth[k] > best) { best = depth[k]; spine = anchor[k]; }
+        const bool with_pose = n_pose > 0 && parts.empty();  // the pose links ride on the first (deepest) chain
+        for (int32_t k = 0; with_pose && k < n_pose; ++k) {  // ... or extend it: the chain reaches the deepest of them
+            const int32_t a = anchor_of(pose_ids[k] - 1);
+            bool above = false, below = false;  // a above (or at) the spine / the spine above a
+            for (int32_t y = spine; y >= 0 && !above; y = m->plink(y)) above = y == a;
+            for (int32_t y = a; y >= 0 && !below; y = m->plink(y)) below = y == spine;
+            if (!above && !below)
+                return set_error(KIN_E_UNSUPPORTED, fn + ": pose link " + std::to_string(k) +
+                                                        " is on another branch than the sphere chain");
+            if (!above) spine = a;
+        }
         std::vector<char> on_path(L, 0);
         for (int32_t y = spine; y >= 0; y = m->plink(y)) on_path[y] = 1;
         std::vector<int32_t> ids, outs;
@@ -263,7 +283,10 @@ int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** 
         kin_coll_desc sub{c->dtype, c->n_q, c->q_joint_ids, (int32_t)ids.size(), ids.data(), cen.data(), rad.data()};
         kin_plan_desc d{c->dtype, c->n_q, c->q_joint_ids, 0, nullptr, spine + 1, c->n_q, c->q_joint_ids, 0};
         auto P = std::make_unique<kin_plan>();
-        if (const int rc = stage_plan(*m, d, &sub, outs.data(), *P)) return rc;
+        if (const int rc = stage_plan(*m, d, &sub, outs.data(), *P, with_pose ? n_pose : 0, pose_ids)) return rc;
+        if (with_pose && P->geom.maxA > kTrajPoseMaxChain)
+            return set_error(KIN_E_UNSUPPORTED, fn + ": the chain to the deepest sphere / pose link has more than " +
+                                                    std::to_string(kTrajPoseMaxChain) + " steps");
         if (const int rc = upload_plan(*P)) return rc;
         parts.push_back(std::move(P));
     }
@@ -288,6 +311,21 @@ int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** 
     }
     *out = top.release();
     return KIN_OK;
+}
+}  // namespace
+
+int kin_coll_plan_create(const kin_model* m, const kin_coll_desc* c, kin_plan** out) {
+    return coll_plan_create(m, c, 0, nullptr, out, "kin_coll_plan_create");
+}
+
+int kin_traj_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose_links, const int32_t* pose_link_ids,
+                         kin_plan** out) {
+    if (n_pose_links < 1 || !pose_link_ids)
+        return set_error(KIN_E_INVALID, "kin_traj_plan_create: need >= 1 pose link (kin_coll_plan_create otherwise)");
+    if (n_pose_links > kTrajMaxPoseLinks)
+        return set_error(KIN_E_UNSUPPORTED, "kin_traj_plan_create: more than " + std::to_string(kTrajMaxPoseLinks) +
+                                                " pose links");
+    return coll_plan_create(m, c, n_pose_links, pose_link_ids, out, "kin_traj_plan_create");
 }
 
 namespace {

@@ -172,6 +172,25 @@ hipError_t launch_traj(const KProg<T>& P, const KStep<T>* steps, const KSphere<T
                        const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minv,
                        T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
 
+// k_traj's POSE variant (kin_traj_opt_pose_batch): one pose link of a kin_traj_plan_create plan held at a
+// per-trajectory target at waypoint wp; compiled for chain bounds 4 and 8
+constexpr int kTrajMaxPoseLinks = 2, kTrajPoseMaxChain = 8;
+template <typename T>
+struct TrajPose {
+    T X[12];          // link frame = frame(step) * X (row-major 3x4)
+    T nu, damp, tol_pos, tol_rot;
+    int32_t step;     // chain step whose post-motion frame carries the link (-1: the root / base frame)
+    int32_t wp;       // the constrained waypoint (0-based, interior)
+    int32_t with_rot;  // 0: 3 rows, 1: 6 rows
+    int32_t pad;
+};
+// targets: [12][ldt] one column per trajectory; info: [6][ldi]
+template <typename T>
+hipError_t launch_traj_pose(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
+                            const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
+                            const TrajPose<T>& tp, const T* minv, const T* targets, int64_t ldt, T* xi, int64_t ldx,
+                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
+
 template <typename T>
 hipError_t launch_pose_residual(const T* poses, int64_t ldp, const T* target, int64_t ldt, int64_t n, int rows, T* vals,
                                 int64_t ldv, hipStream_t st);

@@ -205,6 +205,14 @@ struct kin_plan {
     std::vector<double> col_lo, col_hi;
     mutable std::mutex traj_mu;
     mutable std::map<int32_t, void*> traj_minv;
+    // kin_traj_plan_create: the pose links of kin_traj_opt_pose_batch (fp64 on the host; a kernel argument, never
+    // part of the sphere table): the chain step whose post-motion frame carries the link (-1: the root / base
+    // frame) and the static transform from that frame to the link
+    struct PoseLink {
+        int32_t step;
+        M34 X;
+    };
+    std::vector<PoseLink> pose_links;
     ~kin_plan() {
         for (auto& kv : traj_minv) (void)hipFree(kv.second);
         for (auto& kv : scene_jit) jit_destroy(kv.second);
@@ -217,9 +225,10 @@ struct kin_plan {
 
 namespace kinhip {
 // staging (kinhip_stage.cpp): fills the plan's host program and headers, calls no runtime; coll / sph_out:
-// the spheres of a collision plan and their global indices (null: none / their own order)
+// the spheres of a collision plan and their global indices (null: none / their own order); pose_ids: the
+// n_pose pose links of a kin_traj_plan_create plan (P.pose_links)
 int stage_plan(const kin_model& m, const kin_plan_desc& d, const kin_coll_desc* coll, const int32_t* sph_out,
-               kin_plan& P);
+               kin_plan& P, int32_t n_pose = 0, const int32_t* pose_ids = nullptr);
 int stage_ikc_tree(const kin_model& m, const kin_coll_desc* c, int32_t link_id, kin_plan& P);
 
 // kinhip_host.cpp

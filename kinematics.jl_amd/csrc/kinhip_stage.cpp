@@ -72,6 +72,8 @@ struct Stager {
     const int32_t* sph_out = nullptr;  // global sphere index of each desc sphere (multi-chain plans)
     std::vector<SphD> spheres;
     int32_t sph_root0 = 0, sph_root1 = 0;
+    int32_t n_pose = 0;  // kin_traj_plan_create: pose links (1-based ids)
+    const int32_t* pose_ids = nullptr;
     // a static last edge into the spine folded into Xlast (no step): the spine link and the
     // transform from the previous chain node's canonical frame to it (spheres on the spine, k_ik_coll)
     int32_t fold_spine = -1;
@@ -186,32 +188,55 @@ struct Stager {
     // spheres = links (src/collision.jl:39-49), each carried by the nearest chain node above it;
     // the static path from that node (and the node's canonical-frame correction) is folded into
     // the centre, in fp64
-    int stage_spheres(int32_t sroot) {
+    // The chain frame carrying link lk (0-based): its phase-A step (-1: the root frame) and S, the static
+    // transform from that (canonical) frame down to lk.  `what` names the link in the messages.
+    int carrier(int32_t lk, int32_t sroot, const std::string& what, int32_t* step, M34* S_out) {
         const int32_t L = m.n_links;
         std::vector<int32_t> on_chain(L, -1);
         for (size_t k = 0; k < chain.size(); ++k) on_chain[chain[k]] = (int32_t)k;
+        std::vector<int32_t> path;
+        int32_t x = lk;
+        while (x >= 0 && on_chain[x] < 0) {
+            const int32_t j = m.link_pjoint[x];
+            if (j < 0) break;
+            if (moving[j])
+                return set_error(KIN_E_UNSUPPORTED, "coll plan: " + what + " hangs off a moving joint outside the chain");
+            path.push_back(j);
+            x = m.plink(x);
+        }
+        if (x < 0 || on_chain[x] < 0) return set_error(KIN_E_UNSUPPORTED, "coll plan: " + what + " is on another tree");
+        M34 S = hasX[x] ? Xinv[x] : m_identity();
+        if (x == fold_spine) {  // the spine has no step: carried by the node above it
+            S = fold_X;
+            x = chain[on_chain[x] - 1];
+        }
+        for (size_t pi = path.size(); pi-- > 0;) S = m_mul(S, m.joint_tf(path[pi], m.angles[path[pi]]));
+        *step = (x == sroot) ? -1 : chain_step[on_chain[x]];
+        if (x != sroot && *step < 0) return set_error(KIN_E_INVALID, "coll plan: internal (no step)");
+        *S_out = S;
+        return KIN_OK;
+    }
+
+    // kin_traj_plan_create's pose links: a table of their own (kin_plan::pose_links), never pseudo-spheres
+    int stage_pose_links(int32_t sroot, kin_plan& P) {
+        for (int32_t k = 0; k < n_pose; ++k) {
+            const int32_t lk = pose_ids[k] - 1;
+            if (lk < 0 || lk >= m.n_links) return set_error(KIN_E_KEY, "traj plan: pose link id out of range");
+            kin_plan::PoseLink pl;
+            if (const int rc = carrier(lk, sroot, "pose link " + std::to_string(k), &pl.step, &pl.X)) return rc;
+            P.pose_links.push_back(pl);
+        }
+        return KIN_OK;
+    }
+
+    int stage_spheres(int32_t sroot) {
+        const int32_t L = m.n_links;
         for (int32_t k = 0; k < coll->n_spheres; ++k) {
             const int32_t lk = coll->sphere_link_ids[k] - 1;
             if (lk < 0 || lk >= L) return set_error(KIN_E_KEY, "coll plan: sphere link id out of range");
-            std::vector<int32_t> path;
-            int32_t x = lk;
-            while (x >= 0 && on_chain[x] < 0) {
-                const int32_t j = m.link_pjoint[x];
-                if (j < 0) break;
-                if (moving[j])
-                    return set_error(KIN_E_UNSUPPORTED, "coll plan: sphere " + std::to_string(k) +
-                                                            " hangs off a moving joint outside the chain");
-                path.push_back(j);
-                x = m.plink(x);
-            }
-            if (x < 0 || on_chain[x] < 0)
-                return set_error(KIN_E_UNSUPPORTED, "coll plan: sphere " + std::to_string(k) + " is on another tree");
-            M34 S = hasX[x] ? Xinv[x] : m_identity();
-            if (x == fold_spine) {  // the spine has no step: carry the sphere by the node above it
-                S = fold_X;
-                x = chain[on_chain[x] - 1];
-            }
-            for (size_t pi = path.size(); pi-- > 0;) S = m_mul(S, m.joint_tf(path[pi], m.angles[path[pi]]));
+            int32_t cstep = -1;
+            M34 S;
+            if (const int rc = carrier(lk, sroot, "sphere " + std::to_string(k), &cstep, &S)) return rc;
             SphD sd;
             const double c0 = coll->centers ? coll->centers[3 * k] : 0.0;
             const double c1 = coll->centers ? coll->centers[3 * k + 1] : 0.0;
@@ -219,8 +244,7 @@ struct Stager {
             for (int i = 0; i < 3; ++i) sd.c[i] = S.r[3 * i] * c0 + S.r[3 * i + 1] * c1 + S.r[3 * i + 2] * c2 + S.t[i];
             sd.r = coll->radii[k];
             sd.out = sph_out ? sph_out[k] : k;
-            sd.step = (x == sroot) ? -1 : chain_step[on_chain[x]];
-            if (x != sroot && sd.step < 0) return set_error(KIN_E_INVALID, "coll plan: internal (no step)");
+            sd.step = cstep;
             spheres.push_back(sd);
         }
         std::stable_sort(spheres.begin(), spheres.end(), [](const SphD& a, const SphD& b) { return a.step < b.step; });
@@ -411,6 +435,10 @@ struct Stager {
             const int rc = stage_spheres(sroot);
             if (rc != KIN_OK) return rc;
         }
+        if (n_pose > 0) {
+            const int rc = stage_pose_links(sroot, P);
+            if (rc != KIN_OK) return rc;
+        }
         // ---- phase B ----
         for (auto& pc : pending) {
             const int32_t v = pc.first, u = pc.second;
@@ -543,10 +571,12 @@ struct IkcSphD {
 }  // namespace
 
 int kinhip::stage_plan(const kin_model& m, const kin_plan_desc& d, const kin_coll_desc* coll, const int32_t* sph_out,
-                       kin_plan& P) {
+                       kin_plan& P, int32_t n_pose, const int32_t* pose_ids) {
     Stager st(m, d);
     st.coll = coll;
     st.sph_out = sph_out;
+    st.n_pose = n_pose;
+    st.pose_ids = pose_ids;
     return st.run(P);
 }
 

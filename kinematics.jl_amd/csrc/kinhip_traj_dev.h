@@ -9,8 +9,14 @@
 // differences of the smoothness objective (src/planning.jl:1-28) come from the neighbour lanes; the
 // covariant step Minv g goes through LDS; the line-search decisions are per-segment values held by
 // every lane of the segment (selects, never a divergent branch around a cross-lane operation).
+//
+// POSE = true (kin_traj_opt_pose_batch, chain bounds 4 and 8): a pose link of the plan is held at a per-trajectory
+// target at one interior waypoint.  The walk of traj_penalty also yields the link's frame; the residual norms of
+// lane wp enter the merit; after the Minv g pass the segment's lanes each redo the walk at the broadcast x_wp and
+// solve the 6 x 6 system of the constrained update (traj_pose_newton).  No barrier and no LDS beyond POSE = false.
 #pragma once
 #include "kinhip_coll_dev.h"
+#include "kinhip_ik_dev.h"  // rot_error (the POSE variant's rotation residual)
 
 namespace kinhip {
 namespace {
@@ -56,12 +62,28 @@ __device__ __forceinline__ T pick_col(const T (&x)[ND], int c) {
 //   g[c] = - sum_s weight * r_s * d(d_s)/d(q_c)                  (the half-gradient of pen)
 //   dmin = min_s d_s                                             (+inf unless `interior`)
 // d_s = sdf(centre_s) - radius_s with k_coll's analytic gradient (coll_spheres::finish's columns).
-template <typename T, int MAXA, int ND>
+// traj_penalty's hook: called with the root (base) frame (s = -1) and with every step's post-motion frame.
+// kin_traj_opt_batch's walk has none; the POSE variant captures the frame that carries its pose link.
+struct TrajNoHook {
+    template <typename F>
+    __device__ __forceinline__ void operator()(int, const F&) const {}
+};
+template <typename T>
+struct TrajFrameAt {
+    int step;
+    Fr<T>& out;
+    __device__ __forceinline__ void operator()(int s, const Fr<T>& f) const {
+        if (s == step) out = f;  // (uniform)
+    }
+};
+
+template <typename T, int MAXA, int ND, typename Hook = TrajNoHook>
 __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* __restrict__ S,
                                              const KSphere<T>* __restrict__ sph, const KBox<T>* __restrict__ boxes,
                                              const KAabb<T>* __restrict__ aabb, int na, int nb,
                                              const unsigned char* smem, bool use_lds, const T (&x)[ND], bool interior,
-                                             T trunc, T weight, T (&g)[ND], T& pen, T& dmin) {
+                                             T trunc, T weight, T (&g)[ND], T& pen, T& dmin,
+                                             Hook hook = Hook()) {  // (by value: a reference's temporary changed k_traj's code)
     const bool base = (P.flags & PF_BASE) != 0;
     T bx = T(0), by = T(0), bth = T(0);
     if (base) {
@@ -116,6 +138,7 @@ __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* 
             gb[2] = fma(-cf, fma(-g0, py[0] - by, g1 * (px[0] - bx)), gb[2]);
         }
     };
+    hook(-1, f);
     for (int k = P.sph_root0; k < P.sph_root1; ++k) sphere(-1, sph[k]);
 #pragma unroll
     for (int s = 0; s < MAXA; ++s) {
@@ -125,6 +148,7 @@ __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* 
         rm[s][1] = fma(rz[s][2], o0, -(rz[s][0] * o2));
         rm[s][2] = fma(rz[s][0], o1, -(rz[s][1] * o0));
         for (int k = S[s].sph0; k < S[s].sph1; ++k) sphere(s, sph[k]);
+        hook(s, f);
     }
     // the steps' sums to their q columns (uniform masks)
 #pragma unroll
@@ -143,13 +167,209 @@ __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* 
     }
 }
 
-template <typename T, int MAXA, int L>
+// ---- the POSE variant (kin_traj_opt_pose_batch): one pose link held at a target at waypoint tp.wp ----
+
+// Residual of the pose link carried by chain frame C: r = [p - p*; -log(R* R^T)] (rot_error, k_ik_dls's world
+// axis-angle vector; rows 3..5 are 0 for a position-only constraint) and the link's position p.
+// tg: the target, 3x4 column-major.
+template <typename T>
+__device__ __forceinline__ void traj_pose_residual(const Fr<T>& C, const TrajPose<T>& tp, const T (&tg)[12], T (&r)[6],
+                                                   T (&p)[3]) {
+    Fr<T> Lf;
+    link_frame(Lf, C, true, tp.X);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        p[i] = Lf.t[i];
+        r[i] = Lf.t[i] - tg[9 + i];
+        r[3 + i] = T(0);
+    }
+    if (tp.with_rot) {  // uniform
+        T Rt[9], w[3];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) Rt[3 * a + b] = tg[a + 3 * b];
+        rot_error(Rt, Lf.r, w);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) r[3 + i] = -w[i];
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ void traj_pose_norms(const T (&r)[6], T& rp, T& rr) {
+    rp = sqrt_t(fma(r[0], r[0], fma(r[1], r[1], r[2] * r[2])));
+    rr = sqrt_t(fma(r[3], r[3], fma(r[4], r[4], r[5] * r[5])));
+}
+
+// The Newton correction of the constrained waypoint: with r and the geometric Jacobian J (6 x n_dof; rotation rows
+// 0 for a position-only constraint) at xc,  S = J W^-1 J^T + damp I,  v = S^-1 (-r - J rawc),  u = W^-1 J^T v.
+// xc and rawc are a segment's broadcast values, so every lane of it computes the same u bit for bit.  J's columns
+// [z_j x (p - o_j); z_j] ([z_j; 0] prismatic; the base columns of src/algorithm.jl:98-103) are formed on the fly
+// from the walk's axis and moment vectors, as traj_penalty's sphere gradient does; S is 6 x 6 symmetric positive
+// definite (its rotation block the identity for a position-only constraint): unrolled Cholesky, no pivoting.
+template <typename T, int MAXA, int ND>
+__device__ __forceinline__ void traj_pose_newton(const KProg<T>& P, const KStep<T>* __restrict__ S,
+                                                 const TrajPose<T>& tp, const T (&tg)[12], const TrajDof& dof,
+                                                 const T (&xc)[ND], const T (&rawc)[ND], T (&u)[ND]) {
+    const bool base = (P.flags & PF_BASE) != 0, wr = tp.with_rot != 0;
+    T bx = T(0), by = T(0), bth = T(0);
+    if (base) {
+        bx = pick_col(xc, P.base_col);
+        by = pick_col(xc, P.base_col + 1);
+        bth = pick_col(xc, P.base_col + 2);
+    }
+    Fr<T> f;
+    if (base) base_frame(f, bx, by, bth);
+    else set_identity(f);
+    Fr<T> Cf = f;  // (tp.step = -1: the root frame)
+    T rm[MAXA][3], rz[MAXA][3];
+#pragma unroll
+    for (int s = 0; s < MAXA; ++s) {
+        const T qs = S[s].qcol >= 0 ? pick_col(xc, S[s].qcol) : T(0);
+        step_a<T, KINHIP_COLL_FAST_TRIG != 0>(f, S[s], qs, rm[s], rz[s]);
+        const T o0 = rm[s][0], o1 = rm[s][1], o2 = rm[s][2];  // m_s = z_s x o_s
+        rm[s][0] = fma(rz[s][1], o2, -(rz[s][2] * o1));
+        rm[s][1] = fma(rz[s][2], o0, -(rz[s][0] * o2));
+        rm[s][2] = fma(rz[s][0], o1, -(rz[s][1] * o0));
+        if (s == tp.step) Cf = f;  // uniform
+    }
+    T r[6], p[3];
+    traj_pose_residual(Cf, tp, tg, r, p);
+    // column of step j: z_j x p - m_j
+    auto jcol = [&](int j, T (&Jc)[6]) {
+        if (S[j].jkind == MOT_PRISM) {
+            Jc[0] = rz[j][0]; Jc[1] = rz[j][1]; Jc[2] = rz[j][2];
+            Jc[3] = Jc[4] = Jc[5] = T(0);
+        } else {
+            Jc[0] = fma(rz[j][1], p[2], -(rz[j][2] * p[1])) - rm[j][0];
+            Jc[1] = fma(rz[j][2], p[0], -(rz[j][0] * p[2])) - rm[j][1];
+            Jc[2] = fma(rz[j][0], p[1], -(rz[j][1] * p[0])) - rm[j][2];
+            Jc[3] = wr ? rz[j][0] : T(0); Jc[4] = wr ? rz[j][1] : T(0); Jc[5] = wr ? rz[j][2] : T(0);
+        }
+    };
+    auto bcol = [&](int i, T (&Jc)[6]) {  // base x, y, theta
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Jc[k] = T(0);
+        if (i == 0) Jc[0] = T(1);
+        if (i == 1) Jc[1] = T(1);
+        if (i == 2) {
+            Jc[0] = -(p[1] - by);
+            Jc[1] = p[0] - bx;
+            Jc[5] = wr ? T(1) : T(0);
+        }
+    };
+    // A: the lower triangle of S, row by row (A[i (i + 1) / 2 + j], j <= i); b = -r - J rawc
+    T A[21], b[6];
+#pragma unroll
+    for (int k = 0; k < 21; ++k) A[k] = T(0);
+#pragma unroll
+    for (int i = 0; i < 6; ++i) b[i] = -r[i];
+    auto accumulate = [&](const T (&Jc)[6], T wj, T rj) {
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const T wi = wj * Jc[i];
+#pragma unroll
+            for (int j = 0; j <= i; ++j) A[i * (i + 1) / 2 + j] = fma(wi, Jc[j], A[i * (i + 1) / 2 + j]);
+            b[i] = fma(-Jc[i], rj, b[i]);
+        }
+    };
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) {
+        if (j <= tp.step && (S[j].flags & SF_REC)) {  // uniform
+            const uint64_t m = S[j].colmask;
+            T wj = T(0), rj = T(0);
+#pragma unroll
+            for (int k = 0; k < ND; ++k) {
+                wj = ((m >> k) & 1) ? wj + (T)dof.iW[k] : wj;
+                rj = ((m >> k) & 1) ? rj + rawc[k] : rj;
+            }
+            T Jc[6];
+            jcol(j, Jc);
+            accumulate(Jc, wj, rj);
+        }
+    }
+    if (base) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            T Jc[6];
+            bcol(i, Jc);
+            T wb = T(0);  // (a select chain: the kernel argument is never indexed by a run-time value)
+#pragma unroll
+            for (int k = 0; k < ND; ++k) wb = (P.base_col + i == k) ? (T)dof.iW[k] : wb;
+            accumulate(Jc, wb, pick_col(rawc, P.base_col + i));
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        A[i * (i + 1) / 2 + i] += tp.damp;
+        if (i >= 3 && !wr) A[i * (i + 1) / 2 + i] = T(1);  // (its rows and b are 0: v_rot = 0)
+    }
+    // Cholesky S = L L^T in place, then L y = b, L^T v = y
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        T d = A[j * (j + 1) / 2 + j];
+#pragma unroll
+        for (int q = 0; q < j; ++q) d = fma(-A[j * (j + 1) / 2 + q], A[j * (j + 1) / 2 + q], d);
+        d = sqrt_t(d);
+        A[j * (j + 1) / 2 + j] = d;
+#pragma unroll
+        for (int i = j + 1; i < 6; ++i) {
+            T a = A[i * (i + 1) / 2 + j];
+#pragma unroll
+            for (int q = 0; q < j; ++q) a = fma(-A[i * (i + 1) / 2 + q], A[j * (j + 1) / 2 + q], a);
+            A[i * (i + 1) / 2 + j] = a / d;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        T a = b[i];
+#pragma unroll
+        for (int q = 0; q < i; ++q) a = fma(-A[i * (i + 1) / 2 + q], b[q], a);
+        b[i] = a / A[i * (i + 1) / 2 + i];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        T a = b[i];
+#pragma unroll
+        for (int q = i + 1; q < 6; ++q) a = fma(-A[q * (q + 1) / 2 + i], b[q], a);
+        b[i] = a / A[i * (i + 1) / 2 + i];
+    }
+    // u = W^-1 J^T v, the steps' dot products scattered to their q columns (uniform masks)
+#pragma unroll
+    for (int k = 0; k < ND; ++k) u[k] = T(0);
+#pragma unroll
+    for (int j = 0; j < MAXA; ++j) {
+        if (j <= tp.step && (S[j].flags & SF_REC)) {  // uniform
+            T Jc[6];
+            jcol(j, Jc);
+            const T tj = fma(Jc[0], b[0], fma(Jc[1], b[1], fma(Jc[2], b[2], fma(Jc[3], b[3], fma(Jc[4], b[4], Jc[5] * b[5])))));
+            const uint64_t m = S[j].colmask;
+#pragma unroll
+            for (int k = 0; k < ND; ++k) u[k] = ((m >> k) & 1) ? u[k] + tj : u[k];
+        }
+    }
+    if (base) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            T Jc[6];
+            bcol(i, Jc);
+            const T tj = fma(Jc[0], b[0], fma(Jc[1], b[1], Jc[5] * b[5]));
+#pragma unroll
+            for (int k = 0; k < ND; ++k) u[k] = (P.base_col + i == k) ? u[k] + tj : u[k];
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < ND; ++k) u[k] *= (T)dof.iW[k];
+}
+
+template <typename T, int MAXA, int L, bool POSE = false>
 __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __restrict__ S,
                                           const KSphere<T>* __restrict__ sph, const KBox<T>* __restrict__ boxes,
                                           const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
                                           const T* __restrict__ minvT, T* __restrict__ xi, int64_t ldx, int64_t n_traj,
                                           int32_t* __restrict__ iters, T* __restrict__ info, int64_t ldi,
-                                          unsigned char* smem) {
+                                          unsigned char* smem, const TrajPose<T>* __restrict__ tp = nullptr,
+                                          const T* __restrict__ targets = nullptr, int64_t ldt = 0) {
     constexpr int ND = TrajNd<MAXA>::v;
     const int n_wp = ta.n_wp, ni = n_wp - 2;
     const int ndof = P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
@@ -192,12 +412,31 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
     const int lane = (int)threadIdx.x;
     const int seg0 = lane - w;            // first lane (workgroup-relative) of this segment
     const int wi = min(max(w - 1, 0), ni - 1);  // this lane's row of Minv (clamped: masked below)
+    // POSE: the segment's target, the residual norms of the accepted state (per-segment values, as f)
+    T tg[12], rpc = T(0), rrc = T(0);
+    if constexpr (POSE) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) tg[k] = t < n_traj ? targets[k * ldt + t] : T(0);
+    }
 
     for (int it = 0;; ++it) {
         // ---- the merit and its half-gradient at xn ----
         T pen, dmin;
-        traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc, weight,
-                                  gn, pen, dmin);
+        T rpn = T(0), rrn = T(0);  // POSE: |r_p|, |r_rot| of the segment's candidate
+        if constexpr (POSE) {
+            Fr<T> Cf;
+            set_identity(Cf);
+            traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc,
+                                      weight, gn, pen, dmin, TrajFrameAt<T>{tp->step, Cf});
+            T r[6], pl[3];
+            traj_pose_residual(Cf, *tp, tg, r, pl);
+            traj_pose_norms(r, rpn, rrn);
+            rpn = __shfl(rpn, tp->wp, L);  // lane wp of the segment holds the constrained waypoint
+            rrn = __shfl(rrn, tp->wp, L);
+        } else {
+            traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc,
+                                      weight, gn, pen, dmin);
+        }
         T sm = T(0);
 #pragma unroll
         for (int k = 0; k < ND; ++k) {
@@ -211,14 +450,21 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
             gn[k] = interior ? fma(Wk, ax, gn[k]) : T(0);
             sm = fma(Wk * aw, aw, sm);
         }
-        const T fn = seg_sum<L>(sm + pen);
+        T fl = sm + pen;
+        if constexpr (POSE) fl = (w == tp->wp) ? fl + tp->nu * (rpn + rrn) : fl;  // the exact penalty, on lane wp
+        const T fn = seg_sum<L>(fl);
         const T smn = seg_sum<L>(sm);
         const T dn = seg_min<L>(dmin);
         // ---- accept / reject (per segment: every lane of it holds the same values) ----
         const bool live = !fin;
         const bool acc = it == 0 ? true : (live && fn <= f);
         const bool rej = it > 0 && live && !acc;
-        const bool done = it > 0 && acc && (f - fn < ftol) && (dn >= feas_d);
+        bool done = it > 0 && acc && (f - fn < ftol) && (dn >= feas_d);
+        if constexpr (POSE) {
+            done = done && rpn < tp->tol_pos && rrn < tp->tol_rot;
+            rpc = acc ? rpn : rpc;
+            rrc = acc ? rrn : rrc;
+        }
 #pragma unroll
         for (int k = 0; k < ND; ++k) {
             x[k] = acc ? xn[k] : x[k];
@@ -253,9 +499,27 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         T mx = T(0);
+        if constexpr (POSE) {
+            // ---- raw step, then its projection onto the linearised constraint plus the Newton correction of the
+            // constrained waypoint, spread by the metric's column wp-1 (every lane of a segment: the same u) ----
+            T xc[ND], rawc[ND], u[ND];
+#pragma unroll
+            for (int k = 0; k < ND; ++k) {
+                st[k] = interior && k < ndof ? -(alpha * (st[k] * (T)dof.iW[k])) : T(0);
+                xc[k] = rawc[k] = T(0);
+                if (k >= ndof) continue;  // uniform
+                xc[k] = __shfl(x[k], tp->wp, L);
+                rawc[k] = __shfl(st[k], tp->wp, L);
+            }
+            traj_pose_newton<T, MAXA, ND>(P, S, *tp, tg, dof, xc, rawc, u);
+            const int ci = tp->wp - 1;
+            const T ratio = mt[ci * ni + wi] / mt[ci * ni + ci];
+#pragma unroll
+            for (int k = 0; k < ND; ++k) st[k] = interior && k < ndof ? fma(ratio, u[k], st[k]) : T(0);
+        }
 #pragma unroll
         for (int k = 0; k < ND; ++k) {
-            st[k] = interior && k < ndof ? -(alpha * (st[k] * (T)dof.iW[k])) : T(0);
+            if constexpr (!POSE) st[k] = interior && k < ndof ? -(alpha * (st[k] * (T)dof.iW[k])) : T(0);
             mx = fmax(mx, fabs(st[k]));
         }
         mx = seg_max<L>(mx);
@@ -279,6 +543,10 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
             info[ldi + t] = fsm;
             info[2 * ldi + t] = dcur;
             info[3 * ldi + t] = (T)nacc;
+            if constexpr (POSE) {
+                info[4 * ldi + t] = rpc;
+                info[5 * ldi + t] = rrc;
+            }
         }
     }
 }

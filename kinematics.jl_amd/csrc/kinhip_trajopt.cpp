@@ -1,5 +1,6 @@
 // kinhip_trajopt.cpp -- C-ABI of the batched trajectory optimiser: kin_traj_opt_batch (k_traj,
-// kinhip_traj.hip) and its metric table.
+// kinhip_traj.hip), kin_traj_opt_pose_batch (its POSE variant: one pose link held at a waypoint) and their
+// metric table.
 //
 // Reference semantics restated here (host side):
 //   Objective's A_sub (finite-difference accelerations)    src/planning.jl:1-28
@@ -43,7 +44,7 @@ void traj_metric_inverse(int n_wp, double* out) {
 }
 
 // the plan's device table for n_wp (dtype of the plan); the first call for an n_wp stages it (synchronous)
-int traj_metric_table(const kin_plan* p, int32_t n_wp, void* stream, const void** out) {
+int traj_metric_table(const kin_plan* p, int32_t n_wp, void* stream, const std::string& fn, const void** out) {
     std::lock_guard<std::mutex> lk(p->traj_mu);
     const auto it = p->traj_minv.find(n_wp);
     if (it != p->traj_minv.end()) {
@@ -53,7 +54,7 @@ int traj_metric_table(const kin_plan* p, int32_t n_wp, void* stream, const void*
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess) cs = hipStreamCaptureStatusNone;
     if (cs == hipStreamCaptureStatusActive)
-        return set_error(KIN_E_INVALID, "kin_traj_opt_batch: the plan's first call for this n_wp stages its metric "
+        return set_error(KIN_E_INVALID, fn + ": the plan's first call for this n_wp stages its metric "
                                         "table and cannot run inside a stream capture (make one call outside the "
                                         "capture first)");
     const size_t n = (size_t)(n_wp - 2) * (n_wp - 2);
@@ -63,7 +64,7 @@ int traj_metric_table(const kin_plan* p, int32_t n_wp, void* stream, const void*
     void* d = nullptr;
     const bool f32 = p->dtype == KIN_F32;
     const int rc = upload(&d, {{f32 ? (const void*)hf.data() : (const void*)h.data(), h.size() * (f32 ? 4 : 8), 0}},
-                          "kin_traj_opt_batch");
+                          fn.c_str());
     if (rc != KIN_OK) {
         if (d) (void)hipFree(d);
         return rc;
@@ -86,9 +87,12 @@ int kin_traj_metric_inverse(int32_t n_wp, double* out) {
     return KIN_OK;
 }
 
-int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
-                       int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
-    auto bad = [](int code, const std::string& w) { return set_error(code, "kin_traj_opt_batch: " + w); };
+namespace {
+// kin_traj_opt_batch (pose == null) and kin_traj_opt_pose_batch; fn names the entry point in the messages
+int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+             const kin_traj_pose_params* pose, bool with_pose, const void* targets, int64_t ldt, void* xi, int64_t ldx,
+             int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    auto bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
     // the parameters first (they need no plan), then the plan and the union, then the arrays
     if (!prm) return bad(KIN_E_INVALID, "null parameters");
     if (prm->n_wp < 3 || prm->n_wp > kTrajMaxWp)
@@ -100,6 +104,20 @@ int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_par
     if (!std::isfinite(prm->margin) || !(prm->band >= 0) || !std::isfinite(prm->band) || !(prm->feas >= 0) ||
         !std::isfinite(prm->feas))
         return bad(KIN_E_INVALID, "margin must be finite, band and feas finite and >= 0");
+    if (with_pose) {
+        if (!pose) return bad(KIN_E_INVALID, "null pose parameters");
+        if (pose->n_con != 1) return bad(KIN_E_UNSUPPORTED, "n_con must be 1 (one pose constraint per trajectory)");
+        if (!pose->wp || !pose->with_rot) return bad(KIN_E_INVALID, "null wp / with_rot");
+        if (pose->wp[0] < 1 || pose->wp[0] > prm->n_wp - 2)
+            return bad(KIN_E_INVALID, "wp must be an interior waypoint, 1.." + std::to_string(prm->n_wp - 2));
+        if (pose->with_rot[0] != 0 && pose->with_rot[0] != 1) return bad(KIN_E_INVALID, "with_rot must be 0 or 1");
+        if (!(pose->weight > 0) || !std::isfinite(pose->weight))
+            return bad(KIN_E_INVALID, "pose weight must be finite and > 0");
+        if (!(pose->tol_pos > 0) || !std::isfinite(pose->tol_pos) || !(pose->tol_rot > 0) || !std::isfinite(pose->tol_rot))
+            return bad(KIN_E_INVALID, "tol_pos and tol_rot must be finite and > 0");
+        if (!(pose->damp >= 0) || !std::isfinite(pose->damp)) return bad(KIN_E_INVALID, "damp must be finite and >= 0");
+        if (n_traj > 0 && (!targets || ldt < n_traj)) return bad(KIN_E_INVALID, "bad targets / ldt (ldt >= n_traj)");
+    }
     if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
     if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
     if (!p->parts.empty())
@@ -107,6 +125,10 @@ int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_par
     if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
     if (p->geom.maxA > kTrajMaxChain)
         return bad(KIN_E_UNSUPPORTED, "the sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
+    if (with_pose && p->pose_links.empty())
+        return bad(KIN_E_UNSUPPORTED, "the plan has no pose links (kin_traj_plan_create)");
+    if (with_pose && p->geom.maxA > kTrajPoseMaxChain)
+        return bad(KIN_E_UNSUPPORTED, "the chain has more than " + std::to_string(kTrajPoseMaxChain) + " steps");
     const int nd_max = p->geom.maxA <= 8 ? kTrajNdSmall : kTrajNdLarge;
     if (p->nqcols > nd_max)
         return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(nd_max) + " q columns (+ base) for this chain");
@@ -120,10 +142,10 @@ int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_par
     const int64_t cols = n_traj * prm->n_wp;
     if (!xi || ldx < cols) return bad(KIN_E_INVALID, "bad xi / ldx (ldx >= n_traj * n_wp)");
     if (info && ldi < n_traj) return bad(KIN_E_INVALID, "ldi < n_traj");
-    if (const int rc = check_device(p->device, "kin_traj_opt_batch", "the plan")) return rc;
-    if (const int rc = check_device(sdf->device, "kin_traj_opt_batch", "the kin_sdf")) return rc;
+    if (const int rc = check_device(p->device, fn.c_str(), "the plan")) return rc;
+    if (const int rc = check_device(sdf->device, fn.c_str(), "the kin_sdf")) return rc;
     const void* minv = nullptr;
-    if (const int rc = traj_metric_table(p, prm->n_wp, stream, &minv)) return rc;
+    if (const int rc = traj_metric_table(p, prm->n_wp, stream, fn, &minv)) return rc;
 
     TrajDof dof;
     for (int k = 0; k < kTrajNdLarge; ++k) {
@@ -145,11 +167,39 @@ int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_par
                       {sdf->bh[0], sdf->bh[1], sdf->bh[2]}};
     const hipError_t e = by_dtype(p->dtype, [&](auto t) {
         using T = decltype(t);
-        return launch_traj<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof,
-                              (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
+        if (!with_pose)
+            return launch_traj<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof,
+                                  (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
+        const kin_plan::PoseLink& pl = p->pose_links[0];  // constraint i refers to pose link i
+        TrajPose<T> tp{};
+        to_row12<T>(pl.X, tp.X);
+        tp.nu = (T)pose->weight;
+        tp.damp = (T)pose->damp;
+        tp.tol_pos = (T)pose->tol_pos;
+        tp.tol_rot = (T)pose->tol_rot;
+        tp.step = pl.step;
+        tp.wp = pose->wp[0];
+        tp.with_rot = pose->with_rot[0];
+        return launch_traj_pose<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof, tp,
+                                   (const T*)minv, (const T*)targets, ldt, (T*)xi, ldx, n_traj, iters, (T*)info, ldi,
+                                   (hipStream_t)stream);
     });
     if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj launch: ") + hipGetErrorString(e));
     return KIN_OK;
+}
+}  // namespace
+
+int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
+                       int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    return traj_opt("kin_traj_opt_batch", p, sdf, prm, nullptr, false, nullptr, 0, xi, ldx, n_traj, iters, info, ldi,
+                    stream);
+}
+
+int kin_traj_opt_pose_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+                            const kin_traj_pose_params* pose, const void* targets, int64_t ldt, void* xi, int64_t ldx,
+                            int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    return traj_opt("kin_traj_opt_pose_batch", p, sdf, prm, pose, true, targets, ldt, xi, ldx, n_traj, iters, info, ldi,
+                    stream);
 }
 
 }  // extern "C"

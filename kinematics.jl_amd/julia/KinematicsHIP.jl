@@ -725,6 +725,75 @@ function plan_trajectories!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionC
     Xi, iters, info
 end
 
+# --- a pose constraint at a waypoint on the batched path (kin_traj_plan_create, kin_traj_opt_pose_batch) ---
+
+struct KinTrajPoseParams
+    n_con::Int32
+    wp::Ptr{Int32}
+    with_rot::Ptr{Int32}
+    weight::Float64
+    damp::Float64
+    tol_pos::Float64
+    tol_rot::Float64
+end
+
+"""The collision plan of (sscc, joints) whose staged chain also reaches `link` (kin_traj_plan_create)."""
+function traj_plan!(hm::HIPModel, ::Type{T}, sscc::Kinematics.SweptSphereCollisionChecker, joints::Vector{<:Joint},
+                    link::Link) where {T}
+    ids = Int32[j.id for j in joints]
+    sph = Int32[l.id for l in sscc.sphere_links]
+    key = (:traj, T, ids, sph, link.id)
+    cached_plan!(hm, key, ids) do
+        h = Ref{Ptr{Cvoid}}(C_NULL)
+        r = Float64.(sscc.sphere_radii)
+        pl = Int32[link.id]
+        GC.@preserve ids sph r pl begin
+            d = KinCollDesc(dtype_code(T), length(ids), pointer(ids), length(sph), pointer(sph), C_NULL, pointer(r))
+            check(ccall((:kin_traj_plan_create, libkinhip), Cint,
+                        (Ptr{Cvoid}, Ref{KinCollDesc}, Int32, Ptr{Int32}, Ref{Ptr{Cvoid}}),
+                        hm.handle, d, Int32(1), pointer(pl), h))
+        end
+        h[]
+    end
+end
+
+"""`plan_trajectories_pose!(hm, sscc, joints, sdf, Xi, n_wp, link, wp, targets; with_rot, ...)`: `plan_trajectories!`
+with `link` held at `targets` (n_traj, 12; 3x4 column-major per row) at the interior waypoint `wp` (0-based) of
+every trajectory, position only (`with_rot=false`) or position + orientation: the constrained update of
+include/kinhip.h (kin_traj_opt_pose_batch).  Xi holds the initial guesses (seed the constrained waypoint by IK:
+`inverse_kinematics!` on that row of the straight line, then two straight lines).  Returns (Xi, iters, info):
+info (n_traj, 6) = merit, smoothness term, minimum interior sphere distance, accepted steps, |r_p|, |r_rot|."""
+function plan_trajectories_pose!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionChecker, joints::Vector{<:Joint},
+                                 sdf::HIPSDF, Xi::ROCMatrix{T}, n_wp::Integer, link::Link, wp::Integer,
+                                 targets::ROCMatrix{T}; with_rot::Bool=true, margin::Real=2e-2, band::Real=3e-2,
+                                 weight::Real=10.0, feas::Real=1e-3, ftol::Real=1e-6, max_step::Real=0.5,
+                                 max_iters::Integer=200, dof_weights::Union{Nothing,Vector{Float64}}=nothing,
+                                 pose_weight::Real=10.0, damp::Real=1e-6, tol_pos::Real=1e-3,
+                                 tol_rot::Real=1e-3) where {T}
+    N = size(Xi, 1)
+    N % n_wp == 0 || error("size(Xi, 1) must be a multiple of n_wp")
+    n_traj = div(N, n_wp)
+    size(targets) == (n_traj, 12) || error("targets must be (n_traj, 12)")
+    p = traj_plan!(hm, T, sscc, joints, link)
+    iters = ROCVector{Int32}(undef, n_traj)
+    info = ROCMatrix{T}(undef, n_traj, 6)
+    dw = dof_weights === nothing ? Float64[] : dof_weights
+    wps, rots = Int32[wp], Int32[with_rot ? 1 : 0]
+    GC.@preserve dw wps rots begin
+        prm = Ref(KinTrajParams(Int32(n_wp), Int32(max_iters), Float64(margin), Float64(band), Float64(weight),
+                                Float64(feas), Float64(ftol), Float64(max_step),
+                                dof_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(dw)))
+        pose = Ref(KinTrajPoseParams(Int32(1), pointer(wps), pointer(rots), Float64(pose_weight), Float64(damp),
+                                     Float64(tol_pos), Float64(tol_rot)))
+        check(ccall((:kin_traj_opt_pose_batch, libkinhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{KinTrajParams}, Ref{KinTrajPoseParams}, Ptr{T}, Int64, Ptr{T}, Int64,
+                     Int64, Ptr{Int32}, Ptr{T}, Int64, Ptr{Cvoid}),
+                    p, sdf.handle, prm, pose, pointer(targets), stride(targets, 2), pointer(Xi), stride(Xi, 2), n_traj,
+                    pointer(iters), pointer(info), n_traj, stream_ptr()))
+    end
+    Xi, iters, info
+end
+
 # --- the reference's plan_trajectory with the collision queries on the GPU (src/planning.jl:32-68, 332-401) ---
 
 const HIP_MODELS = WeakKeyDict{Mechanism,HIPModel}()

@@ -19,14 +19,14 @@ from .mechanism import (  # noqa: F401
 from .synth import uniform_configs  # noqa: F401
 from .collision import (  # noqa: F401
     FETCH_ARM_SPHERES, FETCH_LINK_SPHERES, PR2_ARM_SPHERES, PR2_LARM_JOINTS, PR2_MANIP_POSE, PR2_RARM_JOINTS,
-    AttachedUnionSDF, BoxSDF, CollisionIKPlan, CollisionPlan, SweptSphereCollisionChecker, UnionSDF,
+    AttachedUnionSDF, BoxSDF, CollisionIKPlan, CollisionPlan, SweptSphereCollisionChecker, TrajPlan, UnionSDF,
     add_coll_links, add_fetch_arm_spheres, compute_coll_dists, compute_coll_dists_, compute_coll_dists_and_grads,
     compute_coll_dists_and_grads_, compute_swept_sphere, fridge_sdf,
 )
 from .planning import (  # noqa: F401
     ConfigurationConstraint, EqConst, IneqConst, Objective, PoseConstraint, construct_problem,
     collision_aware_ik, create_straight_trajectory, plan_trajectories, plan_trajectory, traj_metric_inverse,
-    traj_opt_batch,
+    traj_opt_batch, traj_opt_pose_batch,
 )
 
 FETCH_ARM_JOINTS = [

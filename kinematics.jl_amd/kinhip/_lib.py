@@ -43,6 +43,7 @@ EXPORTS = [
     "kin_coll_ik_plan_create", "kin_ik_coll_batch", "kin_ik_coll_batch_scene", "kin_sdf_create_attached",
     "kin_coll_batch_scene", "kin_plan_ik_sched_stats", "kin_plan_specialize_scene", "kin_ik_coll_batch_alt",
     "kin_traj_opt_batch", "kin_traj_metric_inverse", "kin_plan_chain_bound",
+    "kin_traj_plan_create", "kin_traj_opt_pose_batch",
 ]
 
 
@@ -94,6 +95,11 @@ class TrajParams(C.Structure):
     _fields_ = [("n_wp", C.c_int32), ("max_iters", C.c_int32), ("margin", C.c_double), ("band", C.c_double),
                 ("weight", C.c_double), ("feas", C.c_double), ("ftol", C.c_double), ("max_step", C.c_double),
                 ("dof_weights", C.c_void_p)]
+
+
+class TrajPoseParams(C.Structure):
+    _fields_ = [("n_con", C.c_int32), ("wp", C.c_void_p), ("with_rot", C.c_void_p), ("weight", C.c_double),
+                ("damp", C.c_double), ("tol_pos", C.c_double), ("tol_rot", C.c_double)]
 
 
 _lib = None
@@ -159,6 +165,8 @@ def lib():
         "kin_traj_opt_batch": ([P, P, P, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_traj_metric_inverse": ([I32, P], C.c_int),
         "kin_plan_chain_bound": ([P, P], C.c_int),
+        "kin_traj_plan_create": ([P, P, I32, P, P], C.c_int),
+        "kin_traj_opt_pose_batch": ([P, P, P, P, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
     # for builds of older sources that lack newer entry points

@@ -124,9 +124,14 @@ class SweptSphereCollisionChecker:
         p = CollisionPlan(self, joints, dtype)
         return p.specialize() if specialize else p
 
+    def traj_plan(self, joints, pose_links, dtype=torch.float64) -> "TrajPlan":
+        """kin_traj_plan_create: this checker's collision plan plus the frames of 1..2 pose links
+        (``traj_opt_pose_batch``, ``plan_trajectories(..., pose_link=...)``)."""
+        return TrajPlan(self, joints, pose_links, dtype)
+
 
 class CollisionPlan:
-    def __init__(self, sscc: SweptSphereCollisionChecker, joints, dtype):
+    def __init__(self, sscc: SweptSphereCollisionChecker, joints, dtype, pose_links=None):
         m = sscc.mech
         m._sync_angles()
         self.dtype = dtype
@@ -138,7 +143,12 @@ class CollisionPlan:
         d = K.CollDesc(_DT[dtype], self._q.size, _p(self._q).value, self._s.size, _p(self._s).value, None,
                        _p(self._r).value)
         self._h = C.c_void_p()
-        K.check(K.lib().kin_coll_plan_create(m._model, C.byref(d), C.byref(self._h)))
+        if pose_links is None:
+            K.check(K.lib().kin_coll_plan_create(m._model, C.byref(d), C.byref(self._h)))
+        else:
+            self._pl = _i32([l.id for l in pose_links])
+            K.check(K.lib().kin_traj_plan_create(m._model, C.byref(d), self._pl.size, _p(self._pl).value,
+                                                 C.byref(self._h)))
         self.device_index = _current_device_index()
 
     def __del__(self):
@@ -243,6 +253,18 @@ def _run_scene(self, sdf, Q, dists, grads, min_dist, truncation, stream, scene_q
 
 
 CollisionPlan._run_scene = _run_scene
+
+
+class TrajPlan(CollisionPlan):
+    """kin_traj_plan_create: a ``CollisionPlan`` (every call that takes one accepts it, with equal results) whose
+    staged chain also reaches `pose_links` (1..2 links on the sphere chain or its extension); constraint i of
+    ``traj_opt_pose_batch`` refers to pose link i."""
+
+    def __init__(self, sscc: SweptSphereCollisionChecker, joints, pose_links, dtype=torch.float64):
+        if isinstance(pose_links, Link):
+            pose_links = [pose_links]
+        self.pose_links = list(pose_links)
+        super().__init__(sscc, joints, dtype, pose_links=self.pose_links)
 
 
 class CollisionIKPlan(Plan):

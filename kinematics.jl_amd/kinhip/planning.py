@@ -21,7 +21,9 @@ SciPy's implementation, not NLopt's -- and reports its status as a symbol.
 ``plan_trajectories`` / ``plan_trajectory(..., solver="GPU")`` are the batched, device-resident
 alternative: ``kin_traj_opt_batch`` runs the whole descent of many trajectories in one kernel (a
 covariant projected gradient on the smoothness objective plus sphere-clearance penalties -- a
-different solver from SLSQP, see include/kinhip.h).
+different solver from SLSQP, see include/kinhip.h).  With one ``PoseConstraint`` of one link
+(``pose_link=`` ...) the same kernel's constrained variant runs (``kin_traj_opt_pose_batch``): the
+link is held at a target pose at one interior waypoint.
 """
 from __future__ import annotations
 
@@ -243,9 +245,54 @@ def traj_opt_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=2e-2,
     return it, nf
 
 
+def traj_opt_pose_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, targets: torch.Tensor, wp: int, with_rot=True,
+                        margin=2e-2, band=3e-2, weight=10.0, feas=1e-3, ftol=1e-6, max_step=0.5, max_iters=200,
+                        dof_weights=None, pose_weight=10.0, damp=1e-6, tol_pos=1e-3, tol_rot=1e-3, iters=None,
+                        info=None, stream=None):
+    """kin_traj_opt_pose_batch in place on X [n_dof, n_traj * n_wp] with a ``TrajPlan``: ``traj_opt_batch`` with the
+    plan's pose link 0 held at targets [12, n_traj] (3x4 column-major, one column per trajectory) at the interior
+    waypoint `wp` (0-based), position only (with_rot False, 3 rows) or position + orientation (6 rows)
+    -> (iters [n_traj] int32, info [6, n_traj]: merit, smoothness term, min interior sphere distance, accepted
+    steps, |r_p|, |r_rot| of the returned state).  X is any initial guess; ``plan_trajectories`` seeds it by IK."""
+    if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
+            or X.shape[1] % int(n_wp) != 0):
+        raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
+    n_traj = X.shape[1] // int(n_wp)
+    if (targets.dtype != plan.dtype or not targets.is_cuda or targets.dim() != 2 or targets.shape != (12, n_traj)
+            or (n_traj > 1 and targets.stride(1) != 1)):
+        raise ValueError(f"targets must be a CUDA {plan.dtype} tensor of shape (12, {n_traj})")
+    _same_device(targets, X, "targets")
+    dev = X.device
+    it = iters if iters is not None else torch.empty(n_traj, dtype=torch.int32, device=dev)
+    nf = info if info is not None else torch.empty((6, n_traj), dtype=plan.dtype, device=dev)
+    if nf.shape != (6, n_traj) or nf.dtype != plan.dtype or it.shape != (n_traj,) or it.dtype != torch.int32:
+        raise ValueError(f"info must be (6, {n_traj}) in the plan dtype and iters ({n_traj},) int32")
+    dw = None if dof_weights is None else np.ascontiguousarray(np.asarray(dof_weights, np.float64))
+    if dw is not None and dw.shape != (plan.n_dof,):
+        raise ValueError(f"dof_weights must have {plan.n_dof} entries")
+    prm = K.TrajParams(int(n_wp), int(max_iters), float(margin), float(band), float(weight), float(feas), float(ftol),
+                       float(max_step), dw.ctypes.data if dw is not None else None)
+    wps, rots = (C.c_int32 * 1)(int(wp)), (C.c_int32 * 1)(1 if with_rot else 0)
+    pp = K.TrajPoseParams(1, C.cast(wps, C.c_void_p), C.cast(rots, C.c_void_p), float(pose_weight), float(damp),
+                          float(tol_pos), float(tol_rot))
+    st = (stream or torch.cuda.current_stream(dev)).cuda_stream
+    K.check(K.lib().kin_traj_opt_pose_batch(plan._h, sdf._h, C.byref(prm), C.byref(pp), targets.data_ptr(),
+                                            max(targets.stride(0), n_traj), X.data_ptr(), X.stride(0), n_traj,
+                                            it.data_ptr(), nf.data_ptr(), nf.stride(0), st))
+    return it, nf
+
+
+def _pose12(T, dtype, dev):
+    """4x4 -> [12, 1] 3x4 column-major on the device."""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return torch.tensor(np.concatenate([T[:3, :3].T.reshape(-1), T[:3, 3]]), dtype=dtype, device=dev).reshape(12, 1)
+
+
 def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, Q_start, Q_goal, n_wp: int,
                       margin=2e-2, band=3e-2, weight=10.0, max_iters=200, dtype=torch.float64, X0=None, stream=None,
-                      feas=1e-3, ftol=1e-6, max_step=0.5, dof_weights=None, plan=None, check_ends=True):
+                      feas=1e-3, ftol=1e-6, max_step=0.5, dof_weights=None, plan=None, check_ends=True,
+                      pose_link=None, pose_wp=None, pose_targets=None, pose_with_rot=True, pose_weight=10.0,
+                      pose_tol=1e-3):
     """Many ``plan_trajectory`` problems in one launch (kin_traj_opt_batch): Q_start / Q_goal [n_dof, n_traj]
     (or one [n_dof] vector for every trajectory) -> (X [n_dof, n_traj * n_wp], iters [n_traj], info [4, n_traj]).
     Trajectory t is X[:, t * n_wp:(t + 1) * n_wp]; it is feasible (every interior sphere distance >= margin -
@@ -253,10 +300,27 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     (create_straight_trajectory) are built on the device unless X0 is given; `check_ends` evaluates every start
     and goal in one kin_coll_batch and raises if one is in collision, as the reference asserts (it reads one
     flag back: pass False to stay asynchronous).  `plan`: a ``CollisionPlan`` of (sscc, joints, dtype) to reuse
-    (its metric table is staged once per n_wp)."""
+    (its metric table is staged once per n_wp).
+
+    With `pose_link`: that link is held at `pose_targets` ([12, n_traj] 3x4 column-major on the device, or one 4x4
+    for every trajectory) at the interior waypoint `pose_wp` (0-based), with its orientation unless
+    `pose_with_rot` is False (kin_traj_opt_pose_batch; `plan` is then a ``TrajPlan`` of (sscc, joints, [pose_link],
+    dtype)).  Unless X0 is given, the constrained waypoint is solved first by the batched IK (kin_ik_dls_batch, 64
+    iterations to 1e-6, from that waypoint of the straight line) and the guess is two straight lines, start -> IK
+    answer -> goal.  info then has 6 rows (4: |r_p|, 5: |r_rot|), and a trajectory with iters[t] <= max_iters also
+    meets the constraint to `pose_tol`."""
     n_wp = int(n_wp)
     dev = _device()
-    plan = plan if plan is not None else sscc.plan(list(joints), dtype=dtype)
+    if pose_link is None:
+        if pose_wp is not None or pose_targets is not None:
+            raise ValueError("pose_wp / pose_targets need pose_link")
+        plan = plan if plan is not None else sscc.plan(list(joints), dtype=dtype)
+    else:
+        if pose_wp is None or pose_targets is None or not 1 <= int(pose_wp) <= n_wp - 2:
+            raise ValueError(f"pose_link needs pose_targets and an interior pose_wp (1..{n_wp - 2})")
+        plan = plan if plan is not None else sscc.traj_plan(list(joints), [pose_link], dtype=dtype)
+        if not getattr(plan, "pose_links", None) or plan.pose_links[0].id != pose_link.id:
+            raise ValueError("plan must be a TrajPlan whose first pose link is pose_link")
     if plan.dtype != dtype:
         raise ValueError("plan dtype differs from dtype")
     n_dof = plan.n_dof
@@ -283,17 +347,44 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
             _, _, mn = plan.run(sdf, torch.cat([Qs, Qg], 1), dists=False, min_dist=True, stream=st)
             if not bool((mn > 0).all()):
                 raise AssertionError("start / goal in collision")
-        if X0 is None:
+        if pose_link is not None:
+            if isinstance(pose_targets, torch.Tensor):
+                tg = pose_targets.to(device=dev, dtype=dtype)
+            else:
+                tg = _pose12(pose_targets, dtype, dev).expand(-1, n_traj)
+            if tg.shape != (12, n_traj):
+                raise ValueError(f"pose_targets must be (12, {n_traj}) or one 4x4 pose")
+            tg = tg.contiguous()
+        i = torch.arange(n_wp, dtype=dtype, device=dev)
+        step = (Qg - Qs) / (n_wp - 1)
+        if X0 is not None:
+            X = torch.as_tensor(X0, dtype=dtype).to(dev).reshape(n_dof, n_traj * n_wp).clone()
+        elif pose_link is None:
             # create_straight_trajectory (src/planning.jl:304-308) per trajectory; the last waypoint is the goal itself
-            step = (Qg - Qs) / (n_wp - 1)
-            i = torch.arange(n_wp, dtype=dtype, device=dev)
             X = (Qs[:, :, None] + step[:, :, None] * i[None, None, :])
             X[:, :, n_wp - 1] = Qg
             X = X.reshape(n_dof, n_traj * n_wp).contiguous()
         else:
-            X = torch.as_tensor(X0, dtype=dtype).to(dev).reshape(n_dof, n_traj * n_wp).clone()
-        it, nf = traj_opt_batch(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
-                                max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
+            # the constrained waypoint by IK from its place on the straight line, then start -> IK answer -> goal
+            c = int(pose_wp)
+            ikp = sscc.mech.plan(list(joints), out_links=[pose_link], jac_link=pose_link, jac_joints=list(joints),
+                                 dtype=dtype)
+            Qm = (Qs + step * c).contiguous()
+            ikp.ik_dls(tg, Qm, max_iters=64, tol_pos=1e-6, tol_rot=1e-6, with_rot=1 if pose_with_rot else 0, stream=st)
+            a, b = (i / c)[None, None, :], ((i - c) / (n_wp - 1 - c))[None, None, :]
+            X = torch.where((i <= c)[None, None, :], Qs[:, :, None] + (Qm - Qs)[:, :, None] * a,
+                            Qm[:, :, None] + (Qg - Qm)[:, :, None] * b)
+            X[:, :, c] = Qm
+            X[:, :, n_wp - 1] = Qg
+            X = X.reshape(n_dof, n_traj * n_wp).contiguous()
+        if pose_link is None:
+            it, nf = traj_opt_batch(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
+                                    max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
+        else:
+            it, nf = traj_opt_pose_batch(plan, sdf, X, n_wp, tg, int(pose_wp), with_rot=pose_with_rot, margin=margin,
+                                         band=band, weight=weight, feas=feas, ftol=ftol, max_step=max_step,
+                                         max_iters=max_iters, dof_weights=dof_weights, pose_weight=pose_weight,
+                                         tol_pos=pose_tol, tol_rot=pose_tol, stream=st)
     return X, it, nf
 
 
@@ -304,17 +395,27 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
     ``solver``: "SLSQP_BOUNDED" (SciPy SLSQP + joint-limit bounds; status ``:SUCCESS`` /
     ``:MAXEVAL_REACHED`` / ``:FAILURE``) or "SCIPY" (the reference's :SCIPY path: no bounds, returns
     SciPy's result).  "NLOPT" and "IPOPT" raise: those libraries are not installed.  "GPU": the batched
-    penalty descent of ``plan_trajectories`` on a batch of one (fp64; no partial constraints; status
-    ``:SUCCESS`` when it ended feasible, else ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used)."""
+    penalty descent of ``plan_trajectories`` on a batch of one (fp64; `partial_consts` empty or exactly one
+    ``PoseConstraint`` with one move link at an interior waypoint, held by the kernel's constrained update with
+    the axis-angle residual to 1e-3; status ``:SUCCESS`` when it ended feasible within `maxiter`, else
+    ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used)."""
     from scipy.optimize import minimize
     from .collision import compute_coll_dists
 
     solver = str(solver).lstrip(":").upper()
     if solver == "GPU":
-        if len(partial_consts):
-            raise ValueError("solver 'GPU' takes no partial constraints")
+        pcs = list(partial_consts)   # (checked before sscc is touched)
+        if len(pcs) > 1 or (pcs and not (isinstance(pcs[0], PoseConstraint) and len(pcs[0].move_links) == 1)):
+            raise ValueError("solver 'GPU' takes at most one partial constraint: a PoseConstraint with one move link")
+        kw = {}
+        if pcs:
+            pc = pcs[0]
+            if not 2 <= pc.idx_wp <= int(n_wp) - 1:
+                raise ValueError(f"solver 'GPU': the PoseConstraint's idx_wp must be interior (2..{int(n_wp) - 1})")
+            kw = dict(pose_link=pc.move_links[0], pose_wp=pc.idx_wp - 1, pose_targets=pc.target_poses[0],
+                      pose_with_rot=pc.with_rots[0])
         X, it, _ = plan_trajectories(sscc, joints, sdf, np.asarray(q_start, np.float64), np.asarray(q_goal, np.float64),
-                                     n_wp, margin=margin, max_iters=maxiter, dtype=torch.float64)
+                                     n_wp, margin=margin, max_iters=maxiter, dtype=torch.float64, **kw)
         return X.cpu().numpy(), (":SUCCESS" if int(it[0]) <= maxiter else ":MAXEVAL_REACHED")
     if solver in ("NLOPT", "IPOPT"):
         raise ValueError(f"solver :{solver} needs a library that is not installed; use 'SLSQP_BOUNDED' "
