@@ -580,6 +580,24 @@ KINHIP_API int kin_traj_opt_pose_batch(const kin_plan* traj_plan, const kin_sdf*
                                        int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
                                        void* stream);
 
+/* kin_traj_opt_batch for robots with spheres on several chains (two arms: the reference's fridge_demo.jl plans the
+ * PR2 with both arms and the base).  Algorithm, parameters, array layouts, iters / info, metric table and capture
+ * rule are kin_traj_opt_batch's; the sphere sum of the merit and of its half-gradient runs over the spheres of
+ * every part (chain program) of a kin_coll_plan_create plan, part after part in plan order (k_traj_tree).  Pinned
+ * against tests/trajopt_ref.py on tests/trajopt_tree_cases.py.  Given a single-chain plan the call is
+ * kin_traj_opt_batch itself (the same kernel, bit-equal results).
+ * Limits (KIN_E_UNSUPPORTED): at most 4 parts; every part's chain at most 16 steps; at most 20 q columns (+ base)
+ * whatever the chain bounds; a static kin_sdf; 3 <= n_wp <= 64.
+ * Not covered: pose constraints on a multi-chain plan (kin_traj_opt_pose_batch keeps refusing such plans, as does
+ * kin_traj_opt_batch) and unions attached to a scene. */
+KINHIP_API int kin_traj_opt_tree_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
+                                       void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
+                                       void* stream);
+/* the chain programs (parts) of a plan: 1 unless kin_coll_plan_create found spheres on several chains; the
+ * compiled chain bound (4 / 8 / 12 / 16 / 32) of part 0 .. count-1 (a single-chain plan: kin_plan_chain_bound) */
+KINHIP_API int kin_plan_part_count(const kin_plan* p, int32_t* out);
+KINHIP_API int kin_plan_part_chain_bound(const kin_plan* p, int32_t part, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -90,6 +90,20 @@ int kin_plan_chain_bound(const kin_plan* p, int32_t* out) {
     return KIN_OK;
 }
 
+int kin_plan_part_count(const kin_plan* p, int32_t* out) {
+    if (!p || !out) return set_error(KIN_E_INVALID, "kin_plan_part_count: null plan / out");
+    *out = p->parts.empty() ? 1 : (int32_t)p->parts.size();
+    return KIN_OK;
+}
+
+int kin_plan_part_chain_bound(const kin_plan* p, int32_t part, int32_t* out) {
+    if (!p || !out) return set_error(KIN_E_INVALID, "kin_plan_part_chain_bound: null plan / out");
+    const int32_t np = p->parts.empty() ? 1 : (int32_t)p->parts.size();
+    if (part < 0 || part >= np) return set_error(KIN_E_INVALID, "kin_plan_part_chain_bound: part out of range");
+    *out = p->parts.empty() ? p->geom.maxA : p->parts[part]->geom.maxA;
+    return KIN_OK;
+}
+
 namespace {
 int plan_run(const kin_plan* p, const void* q, int64_t ldq, int64_t n, void* poses, int64_t ldp, void* jac,
              int64_t ldj, const TileArgs& ta, void* stream, const char* fn) {
@@ -216,6 +230,56 @@ int kin_plan_specialized(const kin_plan* p, uint32_t* kernels) {
 }
 
 namespace {
+// The part table of k_traj_tree (kin_traj_opt_tree_batch) for a multi-chain plan within its limits, one device
+// allocation [TrajPart<T>[n_parts] | steps | spheres]: the parts' program headers, copies of their phase-A steps
+// padded with identity steps to the common bound (so that the kernel's unrolled walk stays inside every staged
+// program) and copies of their sphere tables.  What kin_coll_batch launches for a part (its own steps at its own
+// bound) is untouched.
+int upload_traj_parts(kin_plan& top, const std::string& fn) {
+    const size_t np = top.parts.size();
+    int maxA = 0;
+    for (const auto& s : top.parts) maxA = std::max(maxA, s->geom.maxA);
+    if (np > (size_t)kTrajMaxParts || maxA > kTrajMaxChain) return KIN_OK;  // (refused at the call)
+    const int bound = maxA <= 8 ? 8 : 16;
+    return by_dtype(top.dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        const size_t steps_off = (np * sizeof(TrajPart<T>) + 255) / 256 * 256;
+        size_t bytes = steps_off + np * bound * sizeof(KStep<T>);
+        std::vector<size_t> sph_off(np);
+        for (size_t k = 0; k < np; ++k) {
+            sph_off[k] = bytes;
+            bytes += top.parts[k]->h_sph.size();
+        }
+        std::vector<unsigned char> h(bytes, 0);
+        KStep<T> pad;
+        memset(&pad, 0, sizeof(pad));
+        to_row12<T>(m_identity(), pad.F);
+        to_row12<T>(m_identity(), pad.X);
+        pad.lo = (T)-INFINITY;
+        pad.hi = (T)INFINITY;
+        pad.kind = pad.jkind = MOT_NONE;
+        pad.qcol = pad.out = pad.save = -1;
+        pad.load = LOAD_NONE;
+        for (size_t k = 0; k < np; ++k) {
+            const kin_plan& s = *top.parts[k];
+            TrajPart<T>* tp = reinterpret_cast<TrajPart<T>*>(h.data()) + k;
+            KStep<T>* hs = reinterpret_cast<KStep<T>*>(h.data() + steps_off) + k * bound;
+            tp->P = s.prog<T>();
+            tp->steps_off = (int64_t)(steps_off + k * bound * sizeof(KStep<T>));
+            tp->sph_off = (int64_t)sph_off[k];
+            for (int i = 0; i < bound; ++i) hs[i] = i < s.geom.maxA ? s.host_steps<T>()[i] : pad;
+            memcpy(h.data() + sph_off[k], s.h_sph.data(), s.h_sph.size());
+        }
+        if (const int rc = upload(&top.d_traj_parts, {{h.data(), bytes, 0}}, fn.c_str())) {
+            if (top.d_traj_parts) (void)hipFree(top.d_traj_parts);
+            top.d_traj_parts = nullptr;
+            return rc;
+        }
+        top.traj_tree_maxA = bound;
+        return KIN_OK;
+    });
+}
+
 // kin_coll_plan_create, and with pose links kin_traj_plan_create (fn names the entry point in the messages)
 int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose, const int32_t* pose_ids, kin_plan** out,
                      const std::string& fn) {
@@ -303,6 +367,7 @@ int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose,
         top->device = parts[0]->device;
         top->n_sph = c->n_spheres;
         top->parts = std::move(parts);
+        if (const int rc = upload_traj_parts(*top, fn)) return rc;
     }
     top->n_sph = c->n_spheres;
     for (int32_t k = 0; k < c->n_q; ++k) {  // (kin_traj_opt_batch clamps to these)

@@ -191,6 +191,24 @@ hipError_t launch_traj_pose(const KProg<T>& P, const KStep<T>* steps, const KSph
                             const TrajPose<T>& tp, const T* minv, const T* targets, int64_t ldt, T* xi, int64_t ldx,
                             int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
 
+// k_traj_tree (kin_traj_opt_tree_batch): the spheres of every part of a multi-chain collision plan.  The parts
+// reach the kernel as one device table, staged with the top plan (kin_coll_plan_create): per part the program
+// header, a copy of its steps padded to the plan's common bound (8 or 16: the largest part bound rounded up) and a
+// copy of its spheres, addressed by byte offsets from the table's start (offsets from the kernel argument, not
+// pointers read from memory: the kernel's loads stay global, tests/test_isa.py).
+constexpr int kTrajMaxParts = 4;
+template <typename T>
+struct TrajPart {
+    KProg<T> P;
+    int64_t steps_off;  // KStep<T>[common bound] (identity steps past the part's own program)
+    int64_t sph_off;    // KSphere<T>[P.n_sph]
+};
+// maxA: the common bound (8 or 16); ndof: the plan's q columns (+ base), at most kTrajNdLarge
+template <typename T>
+hipError_t launch_traj_tree(const TrajPart<T>* parts, int n_parts, int maxA, int ndof, const KBox<T>* boxes,
+                            const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minv, T* xi, int64_t ldx,
+                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
+
 template <typename T>
 hipError_t launch_pose_residual(const T* poses, int64_t ldp, const T* target, int64_t ldt, int64_t n, int rows, T* vals,
                                 int64_t ldv, hipStream_t st);

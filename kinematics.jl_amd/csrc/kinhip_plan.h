@@ -213,7 +213,13 @@ struct kin_plan {
         M34 X;
     };
     std::vector<PoseLink> pose_links;
+    // kin_traj_opt_tree_batch: the part table of a multi-chain plan on the device, [TrajPart<T>[n_parts] | every
+    // part's steps padded to traj_tree_maxA | every part's spheres] (kin_coll_plan_create; null when the plan is
+    // past k_traj_tree's limits)
+    void* d_traj_parts = nullptr;
+    int32_t traj_tree_maxA = 0;
     ~kin_plan() {
+        if (d_traj_parts) (void)hipFree(d_traj_parts);
         for (auto& kv : traj_minv) (void)hipFree(kv.second);
         for (auto& kv : scene_jit) jit_destroy(kv.second);
         if (d_ikc) (void)hipFree(d_ikc);

@@ -1,11 +1,12 @@
 // kinhip_trajopt.cpp -- C-ABI of the batched trajectory optimiser: kin_traj_opt_batch (k_traj,
-// kinhip_traj.hip), kin_traj_opt_pose_batch (its POSE variant: one pose link held at a waypoint) and their
-// metric table.
+// kinhip_traj.hip), kin_traj_opt_pose_batch (its POSE variant: one pose link held at a waypoint),
+// kin_traj_opt_tree_batch (k_traj_tree: spheres on several chains) and their metric table.
 //
 // Reference semantics restated here (host side):
 //   Objective's A_sub (finite-difference accelerations)    src/planning.jl:1-28
 //   the two end ConfigurationConstraints of a problem      src/planning.jl:310-330
 #include <cmath>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -88,12 +89,10 @@ int kin_traj_metric_inverse(int32_t n_wp, double* out) {
 }
 
 namespace {
-// kin_traj_opt_batch (pose == null) and kin_traj_opt_pose_batch; fn names the entry point in the messages
-int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
-             const kin_traj_pose_params* pose, bool with_pose, const void* targets, int64_t ldt, void* xi, int64_t ldx,
-             int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
-    auto bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
-    // the parameters first (they need no plan), then the plan and the union, then the arrays
+using Bad = std::function<int(int, const std::string&)>;
+
+// the parameter block: needs no plan and no device
+int traj_check_params(const Bad& bad, const kin_traj_params* prm) {
     if (!prm) return bad(KIN_E_INVALID, "null parameters");
     if (prm->n_wp < 3 || prm->n_wp > kTrajMaxWp)
         return bad(KIN_E_UNSUPPORTED, "n_wp must be in 3.." + std::to_string(kTrajMaxWp) + " (one lane per waypoint of a wave)");
@@ -104,6 +103,65 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
     if (!std::isfinite(prm->margin) || !(prm->band >= 0) || !std::isfinite(prm->band) || !(prm->feas >= 0) ||
         !std::isfinite(prm->feas))
         return bad(KIN_E_INVALID, "margin must be finite, band and feas finite and >= 0");
+    return KIN_OK;
+}
+
+// what follows the plan's own limits: joint limits, dof_weights, the arrays, the devices, the metric table
+// (*minv stays null for n_traj == 0: nothing to launch)
+int traj_check_arrays(const Bad& bad, const std::string& fn, const kin_plan* p, const kin_sdf* sdf,
+                      const kin_traj_params* prm, const void* xi, int64_t ldx, int64_t n_traj, const void* info,
+                      int64_t ldi, void* stream, const void** minv) {
+    *minv = nullptr;
+    if ((int)p->col_lo.size() != p->n_q) return bad(KIN_E_INVALID, "plan without joint limits");
+    const double* dw = prm->dof_weights;
+    for (int k = 0; dw && k < p->nqcols; ++k)
+        if (!(dw[k] > 0) || !std::isfinite(dw[k])) return bad(KIN_E_INVALID, "dof_weights must be finite and > 0");
+    if (n_traj < 0) return bad(KIN_E_INVALID, "n_traj < 0");
+    if (n_traj == 0) return KIN_OK;
+    if (n_traj > (int64_t(1) << 40) / prm->n_wp) return bad(KIN_E_INVALID, "n_traj * n_wp too large");
+    const int64_t cols = n_traj * prm->n_wp;
+    if (!xi || ldx < cols) return bad(KIN_E_INVALID, "bad xi / ldx (ldx >= n_traj * n_wp)");
+    if (info && ldi < n_traj) return bad(KIN_E_INVALID, "ldi < n_traj");
+    if (const int rc = check_device(p->device, fn.c_str(), "the plan")) return rc;
+    if (const int rc = check_device(sdf->device, fn.c_str(), "the kin_sdf")) return rc;
+    return traj_metric_table(p, prm->n_wp, stream, fn, minv);
+}
+
+TrajDof traj_dof(const kin_plan* p, const double* dw) {
+    TrajDof dof;
+    for (int k = 0; k < kTrajNdLarge; ++k) {
+        dof.W[k] = dof.iW[k] = 0.0;
+        dof.lo[k] = -INFINITY;
+        dof.hi[k] = INFINITY;
+    }
+    for (int k = 0; k < p->nqcols; ++k) {
+        const double w = dw ? dw[k] : 1.0;
+        dof.W[k] = w * w;
+        dof.iW[k] = 1.0 / (w * w);
+        if (k < p->n_q) {
+            dof.lo[k] = p->col_lo[k];
+            dof.hi[k] = p->col_hi[k];
+        }
+    }
+    return dof;
+}
+
+TrajArgs traj_args(const kin_traj_params* prm) {
+    return TrajArgs{prm->n_wp, prm->max_iters, prm->margin, prm->band, prm->weight, prm->feas, prm->ftol, prm->max_step};
+}
+
+CollArgs traj_coll_args(const kin_sdf* sdf) {
+    return CollArgs{INFINITY, 0.0, sdf->n_boxes, sdf->n_aabb, 0, 0, {sdf->bc[0], sdf->bc[1], sdf->bc[2]},
+                    {sdf->bh[0], sdf->bh[1], sdf->bh[2]}};
+}
+
+// kin_traj_opt_batch (pose == null) and kin_traj_opt_pose_batch; fn names the entry point in the messages
+int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+             const kin_traj_pose_params* pose, bool with_pose, const void* targets, int64_t ldt, void* xi, int64_t ldx,
+             int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
+    // the parameters first (they need no plan), then the plan and the union, then the arrays
+    if (const int rc = traj_check_params(bad, prm)) return rc;
     if (with_pose) {
         if (!pose) return bad(KIN_E_INVALID, "null pose parameters");
         if (pose->n_con != 1) return bad(KIN_E_UNSUPPORTED, "n_con must be 1 (one pose constraint per trajectory)");
@@ -132,39 +190,13 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
     const int nd_max = p->geom.maxA <= 8 ? kTrajNdSmall : kTrajNdLarge;
     if (p->nqcols > nd_max)
         return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(nd_max) + " q columns (+ base) for this chain");
-    if ((int)p->col_lo.size() != p->n_q) return bad(KIN_E_INVALID, "plan without joint limits");
-    const double* dw = prm->dof_weights;
-    for (int k = 0; dw && k < p->nqcols; ++k)
-        if (!(dw[k] > 0) || !std::isfinite(dw[k])) return bad(KIN_E_INVALID, "dof_weights must be finite and > 0");
-    if (n_traj < 0) return bad(KIN_E_INVALID, "n_traj < 0");
-    if (n_traj == 0) return KIN_OK;
-    if (n_traj > (int64_t(1) << 40) / prm->n_wp) return bad(KIN_E_INVALID, "n_traj * n_wp too large");
-    const int64_t cols = n_traj * prm->n_wp;
-    if (!xi || ldx < cols) return bad(KIN_E_INVALID, "bad xi / ldx (ldx >= n_traj * n_wp)");
-    if (info && ldi < n_traj) return bad(KIN_E_INVALID, "ldi < n_traj");
-    if (const int rc = check_device(p->device, fn.c_str(), "the plan")) return rc;
-    if (const int rc = check_device(sdf->device, fn.c_str(), "the kin_sdf")) return rc;
     const void* minv = nullptr;
-    if (const int rc = traj_metric_table(p, prm->n_wp, stream, fn, &minv)) return rc;
+    if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
+    if (n_traj == 0) return KIN_OK;
 
-    TrajDof dof;
-    for (int k = 0; k < kTrajNdLarge; ++k) {
-        dof.W[k] = dof.iW[k] = 0.0;
-        dof.lo[k] = -INFINITY;
-        dof.hi[k] = INFINITY;
-    }
-    for (int k = 0; k < p->nqcols; ++k) {
-        const double w = dw ? dw[k] : 1.0;
-        dof.W[k] = w * w;
-        dof.iW[k] = 1.0 / (w * w);
-        if (k < p->n_q) {
-            dof.lo[k] = p->col_lo[k];
-            dof.hi[k] = p->col_hi[k];
-        }
-    }
-    const TrajArgs ta{prm->n_wp, prm->max_iters, prm->margin, prm->band, prm->weight, prm->feas, prm->ftol, prm->max_step};
-    const CollArgs ca{INFINITY, 0.0, sdf->n_boxes, sdf->n_aabb, 0, 0, {sdf->bc[0], sdf->bc[1], sdf->bc[2]},
-                      {sdf->bh[0], sdf->bh[1], sdf->bh[2]}};
+    const TrajDof dof = traj_dof(p, prm->dof_weights);
+    const TrajArgs ta = traj_args(prm);
+    const CollArgs ca = traj_coll_args(sdf);
     const hipError_t e = by_dtype(p->dtype, [&](auto t) {
         using T = decltype(t);
         if (!with_pose)
@@ -187,6 +219,40 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
     if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj launch: ") + hipGetErrorString(e));
     return KIN_OK;
 }
+
+// kin_traj_opt_tree_batch: a single-chain plan runs kin_traj_opt_batch's own path (the same k_traj instantiation)
+int traj_opt_tree(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
+                  int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    const std::string fn = "kin_traj_opt_tree_batch";
+    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
+    if (const int rc = traj_check_params(bad, prm)) return rc;
+    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
+    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
+    if (p->parts.empty())
+        return traj_opt(fn, p, sdf, prm, nullptr, false, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
+    if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
+    if ((int)p->parts.size() > kTrajMaxParts)
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
+                                          " chains (parts)");
+    for (const auto& s : p->parts)
+        if (s->geom.maxA > kTrajMaxChain)
+            return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
+    if (p->nqcols > kTrajNdLarge)
+        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
+    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
+    const void* minv = nullptr;
+    if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
+    if (n_traj == 0) return KIN_OK;
+    const TrajDof dof = traj_dof(p, prm->dof_weights);
+    const hipError_t e = by_dtype(p->dtype, [&](auto t) {
+        using T = decltype(t);
+        return launch_traj_tree<T>((const TrajPart<T>*)p->d_traj_parts, (int)p->parts.size(), p->traj_tree_maxA,
+                                   p->nqcols, sdf->boxes<T>(), traj_coll_args(sdf), traj_args(prm), dof, (const T*)minv,
+                                   (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
+    });
+    if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj_tree launch: ") + hipGetErrorString(e));
+    return KIN_OK;
+}
 }  // namespace
 
 int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
@@ -200,6 +266,11 @@ int kin_traj_opt_pose_batch(const kin_plan* p, const kin_sdf* sdf, const kin_tra
                             int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
     return traj_opt("kin_traj_opt_pose_batch", p, sdf, prm, pose, true, targets, ldt, xi, ldx, n_traj, iters, info, ldi,
                     stream);
+}
+
+int kin_traj_opt_tree_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
+                            int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
+    return traj_opt_tree(p, sdf, prm, xi, ldx, n_traj, iters, info, ldi, stream);
 }
 
 }  // extern "C"

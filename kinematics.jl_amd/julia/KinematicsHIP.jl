@@ -725,6 +725,34 @@ function plan_trajectories!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionC
     Xi, iters, info
 end
 
+"""`plan_trajectories_tree!(hm, sscc, joints, sdf, Xi, n_wp; ...)`: `plan_trajectories!` for a checker whose spheres
+hang off several kinematic chains (both arms of a two-armed robot: fridge_demo.jl's `joints = vcat(rarm, larm)`),
+through kin_traj_opt_tree_batch: the same arrays, keywords and results.  At most 4 sphere chains of at most 16
+steps each and 20 dof (base included); with spheres on one chain it is `plan_trajectories!`."""
+function plan_trajectories_tree!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionChecker, joints::Vector{<:Joint},
+                                 sdf::HIPSDF, Xi::ROCMatrix{T}, n_wp::Integer; margin::Real=2e-2, band::Real=3e-2,
+                                 weight::Real=10.0, feas::Real=1e-3, ftol::Real=1e-6, max_step::Real=0.5,
+                                 max_iters::Integer=200, dof_weights::Union{Nothing,Vector{Float64}}=nothing) where {T}
+    N = size(Xi, 1)
+    N % n_wp == 0 || error("size(Xi, 1) must be a multiple of n_wp")
+    n_traj = div(N, n_wp)
+    p = coll_plan!(hm, T, sscc, joints)
+    iters = ROCVector{Int32}(undef, n_traj)
+    info = ROCMatrix{T}(undef, n_traj, 4)
+    dw = dof_weights === nothing ? Float64[] : dof_weights
+    GC.@preserve dw begin
+        prm = Ref(KinTrajParams(Int32(n_wp), Int32(max_iters), Float64(margin), Float64(band), Float64(weight),
+                                Float64(feas), Float64(ftol), Float64(max_step),
+                                dof_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(dw)))
+        check(ccall((:kin_traj_opt_tree_batch, libkinhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{KinTrajParams}, Ptr{T}, Int64, Int64, Ptr{Int32}, Ptr{T}, Int64,
+                     Ptr{Cvoid}),
+                    p, sdf.handle, prm, pointer(Xi), stride(Xi, 2), n_traj, pointer(iters), pointer(info), n_traj,
+                    stream_ptr()))
+    end
+    Xi, iters, info
+end
+
 # --- a pose constraint at a waypoint on the batched path (kin_traj_plan_create, kin_traj_opt_pose_batch) ---
 
 struct KinTrajPoseParams

@@ -44,6 +44,7 @@ EXPORTS = [
     "kin_coll_batch_scene", "kin_plan_ik_sched_stats", "kin_plan_specialize_scene", "kin_ik_coll_batch_alt",
     "kin_traj_opt_batch", "kin_traj_metric_inverse", "kin_plan_chain_bound",
     "kin_traj_plan_create", "kin_traj_opt_pose_batch",
+    "kin_traj_opt_tree_batch", "kin_plan_part_count", "kin_plan_part_chain_bound",
 ]
 
 
@@ -167,6 +168,9 @@ def lib():
         "kin_plan_chain_bound": ([P, P], C.c_int),
         "kin_traj_plan_create": ([P, P, I32, P, P], C.c_int),
         "kin_traj_opt_pose_batch": ([P, P, P, P, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
+        "kin_traj_opt_tree_batch": ([P, P, P, P, I64, I64, P, P, I64, P], C.c_int),
+        "kin_plan_part_count": ([P, P], C.c_int),
+        "kin_plan_part_chain_bound": ([P, I32, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
     # for builds of older sources that lack newer entry points

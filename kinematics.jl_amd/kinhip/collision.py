@@ -182,6 +182,23 @@ class CollisionPlan:
         K.check(K.lib().kin_plan_chain_bound(self._h, C.byref(v)))
         return v.value
 
+    @property
+    def n_parts(self) -> int:
+        """kin_plan_part_count: the chain programs of the plan (1 unless the spheres hang off several chains)."""
+        v = C.c_int32()
+        K.check(K.lib().kin_plan_part_count(self._h, C.byref(v)))
+        return v.value
+
+    @property
+    def part_chain_bounds(self) -> list:
+        """kin_plan_part_chain_bound of every part, in plan order."""
+        out = []
+        for k in range(self.n_parts):
+            v = C.c_int32()
+            K.check(K.lib().kin_plan_part_chain_bound(self._h, k, C.byref(v)))
+            out.append(v.value)
+        return out
+
     def run(self, sdf: UnionSDF, Q: torch.Tensor, dists=True, grads=False, min_dist=False,
             truncation=float("inf"), stream=None, scene_q: Optional[torch.Tensor] = None):
         """-> (dists [n_sph, N] | None, grads [n_sph, n_dof, N] | None, min_dist [N] | None). Async.

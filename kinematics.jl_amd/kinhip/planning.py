@@ -23,7 +23,8 @@ alternative: ``kin_traj_opt_batch`` runs the whole descent of many trajectories 
 covariant projected gradient on the smoothness objective plus sphere-clearance penalties -- a
 different solver from SLSQP, see include/kinhip.h).  With one ``PoseConstraint`` of one link
 (``pose_link=`` ...) the same kernel's constrained variant runs (``kin_traj_opt_pose_batch``): the
-link is held at a target pose at one interior waypoint.
+link is held at a target pose at one interior waypoint.  A checker whose spheres hang off several chains
+(two arms) runs ``kin_traj_opt_tree_batch`` (``traj_opt_tree_batch``; no pose constraint there).
 """
 from __future__ import annotations
 
@@ -227,6 +228,22 @@ def traj_opt_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=2e-2,
     the end columns of every trajectory stay as given) with a ``CollisionPlan`` -> (iters [n_traj] int32,
     info [4, n_traj]: merit, smoothness term, min interior sphere distance, accepted steps).  Async on the stream
     after the plan's first call for this n_wp (which stages the metric table)."""
+    return _traj_opt(K.lib().kin_traj_opt_batch, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step,
+                     max_iters, dof_weights, iters, info, stream)
+
+
+def traj_opt_tree_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=2e-2, band=3e-2, weight=10.0,
+                        feas=1e-3, ftol=1e-6, max_step=0.5, max_iters=200, dof_weights=None, iters=None, info=None,
+                        stream=None):
+    """kin_traj_opt_tree_batch: ``traj_opt_batch`` for a ``CollisionPlan`` whose spheres hang off several chains
+    (``plan.n_parts`` > 1, e.g. both arms of a two-armed robot); the same arrays and results.  A single-chain plan
+    runs ``traj_opt_batch``'s kernel."""
+    return _traj_opt(K.lib().kin_traj_opt_tree_batch, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step,
+                     max_iters, dof_weights, iters, info, stream)
+
+
+def _traj_opt(entry, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step, max_iters, dof_weights, iters,
+              info, stream):
     if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
             or X.shape[1] % int(n_wp) != 0):
         raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
@@ -240,8 +257,8 @@ def traj_opt_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=2e-2,
     prm = K.TrajParams(int(n_wp), int(max_iters), float(margin), float(band), float(weight), float(feas), float(ftol),
                        float(max_step), dw.ctypes.data if dw is not None else None)
     st = (stream or torch.cuda.current_stream(dev)).cuda_stream
-    K.check(K.lib().kin_traj_opt_batch(plan._h, sdf._h, C.byref(prm), X.data_ptr(), X.stride(0), n_traj,
-                                       it.data_ptr(), nf.data_ptr(), nf.stride(0), st))
+    K.check(entry(plan._h, sdf._h, C.byref(prm), X.data_ptr(), X.stride(0), n_traj, it.data_ptr(), nf.data_ptr(),
+                  nf.stride(0), st))
     return it, nf
 
 
@@ -318,6 +335,9 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     else:
         if pose_wp is None or pose_targets is None or not 1 <= int(pose_wp) <= n_wp - 2:
             raise ValueError(f"pose_link needs pose_targets and an interior pose_wp (1..{n_wp - 2})")
+        if (plan if plan is not None else sscc.plan(list(joints), dtype=dtype)).n_parts > 1:
+            raise ValueError("pose_link: the checker's spheres hang off several chains (kin_traj_opt_pose_batch "
+                             "takes one sphere chain)")
         plan = plan if plan is not None else sscc.traj_plan(list(joints), [pose_link], dtype=dtype)
         if not getattr(plan, "pose_links", None) or plan.pose_links[0].id != pose_link.id:
             raise ValueError("plan must be a TrajPlan whose first pose link is pose_link")
@@ -378,8 +398,9 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
             X[:, :, n_wp - 1] = Qg
             X = X.reshape(n_dof, n_traj * n_wp).contiguous()
         if pose_link is None:
-            it, nf = traj_opt_batch(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
-                                    max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
+            opt = traj_opt_tree_batch if plan.n_parts > 1 else traj_opt_batch
+            it, nf = opt(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
+                         max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
         else:
             it, nf = traj_opt_pose_batch(plan, sdf, X, n_wp, tg, int(pose_wp), with_rot=pose_with_rot, margin=margin,
                                          band=band, weight=weight, feas=feas, ftol=ftol, max_step=max_step,

@@ -6,6 +6,14 @@ the host, one GPU constraint evaluation per iterate) looped over the same 32 pro
 (a penalty descent vs SLSQP on the constrained problem): the comparison is on feasibility and time, not iterates.
 
     python tools/traj_bench.py [--reps 5] [--no-slsqp] [--out profiles/traj_bench.json]
+    python tools/traj_bench.py --scene pr2 [--out profiles/traj_bench_pr2.json]
+
+--scene pr2: the reference's fridge_demo.jl shape -- the PR2 (tests/golden/pr2_two_arms.urdf) with both arms and
+the planar base (17 columns), kinhip.PR2_ARM_SPHERES on two chains (kin_traj_opt_tree_batch), the static fridge
+union at door 2.0 and base (1.2, 0, 0), from PR2_MANIP_POSE to 32 collision-free goals at the fridge (random arm
+offsets of up to +-0.6 rad, the base driven 0.2-0.7 towards the fridge, +-0.15 sideways and turned by up to +-0.3,
+from default_rng(0); the first 32 with every sphere more than 0.05 clear).  straight_infeasible_of_32 counts the
+problems whose straight line does not clear the fridge by margin - feas.
 
 Timing: a host clock around calls that end in a device synchronise, after a warm-up call per shape; the median of
 --reps repeats and their min / max.  Iterations per second counts, per trajectory, the iterations the kernel ran
@@ -40,6 +48,32 @@ def scene():
     T[:3, 3] = (0.4, -0.25, 0.7)
     sdf = kinhip.UnionSDF([kinhip.BoxSDF(T, (0.05, 0.05, 0.5))])
     return m, joints, sscc, sdf
+
+
+def scene_pr2():
+    m = kinhip.parse_urdf(os.path.join(ROOT, "tests", "golden", "pr2_two_arms.urdf"), with_base=True)
+    joints = [m.find_joint(n) for n in kinhip.PR2_RARM_JOINTS + kinhip.PR2_LARM_JOINTS]
+    m.set_joint_angles([m.find_joint("torso_lift_joint")], [kinhip.PR2_MANIP_POSE[2], 0.0, 0.0, 0.0])
+    sscc = kinhip.SweptSphereCollisionChecker(m)
+    for name, c, r in kinhip.PR2_ARM_SPHERES:
+        sscc.add_coll_sphere(m.find_link(name), c, r)
+    fridge = kinhip.parse_urdf(os.path.join(ROOT, "tests", "golden", "fridge.urdf"), with_base=True)
+    return m, joints, sscc, kinhip.fridge_sdf(fridge)
+
+
+def goals_pr2(joints, sscc, sdf, q_start, n=32):
+    """The first n collision-free (min d > 0.05) random offsets of q_start, clipped to the joint limits."""
+    N = 4096
+    rng = np.random.default_rng(0)
+    Q = q_start[:, None] + np.concatenate([rng.uniform(-0.6, 0.6, (14, N)), rng.uniform(0.2, 0.7, (1, N)),
+                                           rng.uniform(-0.15, 0.15, (1, N)), rng.uniform(-0.3, 0.3, (1, N))])
+    lo = np.array([j.lower_limit for j in joints] + [-np.inf] * 3)
+    hi = np.array([j.upper_limit for j in joints] + [np.inf] * 3)
+    Q = torch.tensor(np.clip(Q, lo[:, None], hi[:, None]), dtype=torch.float64, device="cuda")
+    _, _, mn = sscc.plan(joints, dtype=torch.float64).run(sdf, Q, dists=False, min_dist=True)
+    ok = (mn > 0.05).nonzero()[:n, 0]
+    assert ok.numel() == n, int(ok.numel())
+    return Q[:, ok].contiguous()
 
 
 def goals(m, joints, sscc, sdf, n=32):
@@ -79,14 +113,28 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-slsqp", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--scene", choices=("fetch", "pr2"), default="fetch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("traj_bench.py needs a GPU")
-    m, joints, sscc, sdf = scene()
-    G = goals(m, joints, sscc, sdf)
-    q_start = np.zeros(8)
+    if a.scene == "pr2":
+        m, joints, sscc, sdf = scene_pr2()
+        ra, la, _ = kinhip.PR2_MANIP_POSE
+        q_start = np.concatenate([np.deg2rad(np.array(ra + la)), np.zeros(3)])
+        G = goals_pr2(joints, sscc, sdf, q_start)
+        name = "pr2, both arms + base, fridge (door 2.0, base (1.2, 0, 0)), 32 collision-free goals"
+    else:
+        m, joints, sscc, sdf = scene()
+        G = goals(m, joints, sscc, sdf)
+        q_start = np.zeros(8)
+        name = "fetch + thin box, 32 IK goals"
     cp64 = sscc.plan(joints, dtype=torch.float64)
-    res = {"scene": "fetch + thin box, 32 IK goals", "n_wp": N_WP, "max_iters": MAX_ITERS, "gpu": []}
+    qs = torch.tensor(q_start, dtype=torch.float64, device="cuda")[:, None, None]
+    lines = qs + (G[:, :, None] - qs) * (torch.arange(N_WP, dtype=torch.float64, device="cuda") / (N_WP - 1))
+    d0 = interior_clearance(cp64, sdf, lines.reshape(len(q_start), 32 * N_WP).contiguous(), 32)
+    res = {"scene": name, "n_wp": N_WP, "max_iters": MAX_ITERS, "parts": cp64.n_parts,
+           "straight_infeasible_of_32": int((d0 < MARGIN - FEAS).sum()), "gpu": []}
+    print(json.dumps({k: v for k, v in res.items() if k != "gpu"}), flush=True)
     for dtype in (torch.float32, torch.float64):
         cp = sscc.plan(joints, dtype=dtype)
         for n_traj in (32, 1024, 32768):
