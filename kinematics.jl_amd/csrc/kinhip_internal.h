@@ -166,12 +166,6 @@ struct TrajDof {
     double W[kTrajNdLarge], iW[kTrajNdLarge];  // dof_weights^2 and its reciprocal
     double lo[kTrajNdLarge], hi[kTrajNdLarge];  // joint limits (base columns unbounded)
 };
-// minv: (A_sub[I,I])^-1 of n_wp waypoints on the device, row-major (symmetric, so also its transpose)
-template <typename T>
-hipError_t launch_traj(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
-                       const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minv,
-                       T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
-
 // k_traj's POSE variant (kin_traj_opt_pose_batch): one pose link of a kin_traj_plan_create plan held at a
 // per-trajectory target at waypoint wp; compiled for chain bounds 4 and 8
 constexpr int kTrajMaxPoseLinks = 2, kTrajPoseMaxChain = 8;
@@ -184,13 +178,6 @@ struct TrajPose {
     int32_t with_rot;  // 0: 3 rows, 1: 6 rows
     int32_t pad;
 };
-// targets: [12][ldt] one column per trajectory; info: [6][ldi]
-template <typename T>
-hipError_t launch_traj_pose(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
-                            const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
-                            const TrajPose<T>& tp, const T* minv, const T* targets, int64_t ldt, T* xi, int64_t ldx,
-                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
-
 // k_traj_tree (kin_traj_opt_tree_batch): the spheres of every part of a multi-chain collision plan.  The parts
 // reach the kernel as one device table, staged with the top plan (kin_coll_plan_create): per part the program
 // header, a copy of its steps padded to the plan's common bound (8 or 16: the largest part bound rounded up) and a
@@ -203,11 +190,25 @@ struct TrajPart {
     int64_t steps_off;  // KStep<T>[common bound] (identity steps past the part's own program)
     int64_t sph_off;    // KSphere<T>[P.n_sph]
 };
-// maxA: the common bound (8 or 16); ndof: the plan's q columns (+ base), at most kTrajNdLarge
+// One launcher for the three kernels; the descriptor says which one and carries what only that one takes.
 template <typename T>
-hipError_t launch_traj_tree(const TrajPart<T>* parts, int n_parts, int maxA, int ndof, const KBox<T>* boxes,
-                            const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minv, T* xi, int64_t ldx,
-                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st);
+struct TrajLaunch {
+    const KProg<T>* P;  // the chain (k_traj, k_traj_pose; unused by k_traj_tree)
+    const KStep<T>* steps;
+    const KSphere<T>* sph;
+    int maxA;  // the chain bound (tree: the common bound, 8 or 16); one the variant is not compiled for is refused
+    int ndof;  // the plan's q columns (+ base); tree: at most kTrajNdLarge
+    const TrajPose<T>* tp = nullptr;  // k_traj_pose (else null): targets [12][ldt], one column per trajectory; info [6][ldi]
+    const T* targets = nullptr;
+    int64_t ldt = 0;
+    const TrajPart<T>* parts = nullptr;  // k_traj_tree (else null)
+    int n_parts = 0;
+};
+// minv: (A_sub[I,I])^-1 of n_wp waypoints on the device, row-major (symmetric, so also its transpose)
+template <typename T>
+hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollArgs& a, const TrajArgs& ta,
+                       const TrajDof& dof, const T* minv, T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info,
+                       int64_t ldi, hipStream_t st);
 
 template <typename T>
 hipError_t launch_pose_residual(const T* poses, int64_t ldp, const T* target, int64_t ldt, int64_t n, int rows, T* vals,

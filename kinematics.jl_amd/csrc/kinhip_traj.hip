@@ -40,7 +40,8 @@ __global__ __launch_bounds__(256) void k_traj_tree(const TrajPart<T>* __restrict
                                                    T* __restrict__ xi, int64_t ldx, int64_t n_traj,
                                                    int32_t* __restrict__ iters, T* __restrict__ info, int64_t ldi) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    traj_tree_body<T, MAXA, L>(parts, n_parts, ndof, boxes, a, ta, dof, minvT, xi, ldx, n_traj, iters, info, ldi, smem);
+    traj_body<T, MAXA, L, false, true>(KProg<T>{}, nullptr, nullptr, boxes, a, ta, dof, minvT, xi, ldx, n_traj, iters, info,
+                                       ldi, smem, nullptr, nullptr, 0, parts, n_parts, ndof);
 }
 
 }  // namespace
@@ -53,16 +54,37 @@ size_t traj_lds_bytes(int n_boxes, int n_wp, int ndof, int block) {
     return box + sizeof(T) * ((size_t)(n_wp - 2) * (n_wp - 2) + (size_t)block * ndof);
 }
 
+namespace {
+
+// f(m, l), two std::integral_constant, for the chain bound of the list that equals maxA and the segment size L
+// (one of traj_segment's); false if the list has no such bound
+template <int... MA, typename F>
+bool traj_dispatch(int maxA, int L, F&& f) {
+    const auto at = [&](auto m) {
+        switch (L) {
+        case 8: f(m, std::integral_constant<int, 8>{}); break;
+        case 16: f(m, std::integral_constant<int, 16>{}); break;
+        case 32: f(m, std::integral_constant<int, 32>{}); break;
+        default: f(m, std::integral_constant<int, 64>{}); break;
+        }
+        return true;
+    };
+    return (... || (maxA == MA && at(std::integral_constant<int, MA>{})));
+}
+
+}  // namespace
+
+// d.tp selects k_traj_pose, d.parts k_traj_tree, neither k_traj; each with the chain bounds it is compiled for
 template <typename T>
-hipError_t launch_traj(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
-                       const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minvT,
-                       T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st) {
+hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollArgs& a, const TrajArgs& ta,
+                       const TrajDof& dof, const T* minvT, T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info,
+                       int64_t ldi, hipStream_t st) {
+    if (d.parts && (d.n_parts < 1 || d.n_parts > kTrajMaxParts || d.ndof > kTrajNdLarge)) return hipErrorInvalidValue;
     const int L = traj_segment(ta.n_wp);
-    const int ndof = P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
     // the largest workgroup (whole waves) whose LDS stays within 64 KiB
     int block = 256;
-    while (block > 64 && traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block) > 65536) block /= 2;
-    const size_t lds = traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block);
+    while (block > 64 && traj_lds_bytes<T>(a.n_boxes, ta.n_wp, d.ndof, block) > 65536) block /= 2;
+    const size_t lds = traj_lds_bytes<T>(a.n_boxes, ta.n_wp, d.ndof, block);
     if (lds > 65536) return hipErrorInvalidValue;
     // chunks of trajectories: every lane byte offset (column * sizeof(T)) below 2^31
     const int64_t chunk = kChunk / 64;
@@ -70,126 +92,37 @@ hipError_t launch_traj(const KProg<T>& P, const KStep<T>* steps, const KSphere<T
         const int64_t c = std::min(chunk, n_traj - t0);
         const dim3 grid(grid_of(c * L, block)), blk(block);
         T* xc = xi + t0 * ta.n_wp;
+        const T* tc = d.targets ? d.targets + t0 : d.targets;
         int32_t* ic = iters ? iters + t0 : iters;
         T* fc = info ? info + t0 : info;
-#define KIN_TR_LAUNCH_L(MA, LL) \
-        hipLaunchKernelGGL((k_traj<T, MA, LL>), grid, blk, lds, st, P, steps, sph, boxes, a, ta, dof, minvT, xc, ldx, c, ic, fc, ldi)
-#define KIN_TR_LAUNCH(MA)                      \
-        switch (L) {                           \
-        case 8: KIN_TR_LAUNCH_L(MA, 8); break;   \
-        case 16: KIN_TR_LAUNCH_L(MA, 16); break; \
-        case 32: KIN_TR_LAUNCH_L(MA, 32); break; \
-        default: KIN_TR_LAUNCH_L(MA, 64); break; \
-        }
-        switch (g.maxA) {
-        case 4: KIN_TR_LAUNCH(4); break;
-        case 8: KIN_TR_LAUNCH(8); break;
-        case 12: KIN_TR_LAUNCH(12); break;
-        case 16: KIN_TR_LAUNCH(16); break;
-        default: return hipErrorInvalidValue;  // (kin_traj_opt_batch refuses longer chains)
-        }
-#undef KIN_TR_LAUNCH
-#undef KIN_TR_LAUNCH_L
+        bool compiled;  // (the entry points refuse the chain bounds a variant is not compiled for)
+        if (!d.tp && !d.parts)
+            compiled = traj_dispatch<4, 8, 12, 16>(d.maxA, L, [&](auto m, auto l) {
+                hipLaunchKernelGGL((k_traj<T, decltype(m)::value, decltype(l)::value>), grid, blk, lds, st, *d.P, d.steps,
+                                   d.sph, boxes, a, ta, dof, minvT, xc, ldx, c, ic, fc, ldi);
+            });
+        else if (d.tp)
+            compiled = traj_dispatch<4, 8>(d.maxA, L, [&](auto m, auto l) {
+                hipLaunchKernelGGL((k_traj_pose<T, decltype(m)::value, decltype(l)::value>), grid, blk, lds, st, *d.P,
+                                   d.steps, d.sph, boxes, a, ta, dof, *d.tp, minvT, tc, d.ldt, xc, ldx, c, ic, fc, ldi);
+            });
+        else
+            compiled = traj_dispatch<8, 16>(d.maxA, L, [&](auto m, auto l) {
+                hipLaunchKernelGGL((k_traj_tree<T, decltype(m)::value, decltype(l)::value>), grid, blk, lds, st, d.parts,
+                                   d.n_parts, d.ndof, boxes, a, ta, dof, minvT, xc, ldx, c, ic, fc, ldi);
+            });
+        if (!compiled) return hipErrorInvalidValue;
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-template <typename T>
-hipError_t launch_traj_pose(const KProg<T>& P, const KStep<T>* steps, const KSphere<T>* sph, const KBox<T>* boxes,
-                            const LaunchGeom& g, const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
-                            const TrajPose<T>& tp, const T* minvT, const T* targets, int64_t ldt, T* xi, int64_t ldx,
-                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st) {
-    const int L = traj_segment(ta.n_wp);
-    const int ndof = P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
-    int block = 256;  // as launch_traj: the same LDS layout
-    while (block > 64 && traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block) > 65536) block /= 2;
-    const size_t lds = traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block);
-    if (lds > 65536) return hipErrorInvalidValue;
-    const int64_t chunk = kChunk / 64;
-    for (int64_t t0 = 0; t0 < n_traj; t0 += chunk) {
-        const int64_t c = std::min(chunk, n_traj - t0);
-        const dim3 grid(grid_of(c * L, block)), blk(block);
-        T* xc = xi + t0 * ta.n_wp;
-        const T* tc = targets + t0;
-        int32_t* ic = iters ? iters + t0 : iters;
-        T* fc = info ? info + t0 : info;
-#define KIN_TRP_LAUNCH_L(MA, LL)                                                                                    \
-        hipLaunchKernelGGL((k_traj_pose<T, MA, LL>), grid, blk, lds, st, P, steps, sph, boxes, a, ta, dof, tp, minvT, tc, \
-                           ldt, xc, ldx, c, ic, fc, ldi)
-#define KIN_TRP_LAUNCH(MA)                        \
-        switch (L) {                              \
-        case 8: KIN_TRP_LAUNCH_L(MA, 8); break;   \
-        case 16: KIN_TRP_LAUNCH_L(MA, 16); break; \
-        case 32: KIN_TRP_LAUNCH_L(MA, 32); break; \
-        default: KIN_TRP_LAUNCH_L(MA, 64); break; \
-        }
-        switch (g.maxA) {
-        case 4: KIN_TRP_LAUNCH(4); break;
-        case 8: KIN_TRP_LAUNCH(8); break;
-        default: return hipErrorInvalidValue;  // (kin_traj_opt_pose_batch refuses longer chains)
-        }
-#undef KIN_TRP_LAUNCH
-#undef KIN_TRP_LAUNCH_L
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-template <typename T>
-hipError_t launch_traj_tree(const TrajPart<T>* parts, int n_parts, int maxA, int ndof, const KBox<T>* boxes,
-                            const CollArgs& a, const TrajArgs& ta, const TrajDof& dof, const T* minvT, T* xi, int64_t ldx,
-                            int64_t n_traj, int32_t* iters, T* info, int64_t ldi, hipStream_t st) {
-    if (n_parts < 1 || n_parts > kTrajMaxParts || ndof > kTrajNdLarge) return hipErrorInvalidValue;
-    const int L = traj_segment(ta.n_wp);
-    int block = 256;  // as launch_traj: the same LDS layout
-    while (block > 64 && traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block) > 65536) block /= 2;
-    const size_t lds = traj_lds_bytes<T>(a.n_boxes, ta.n_wp, ndof, block);
-    if (lds > 65536) return hipErrorInvalidValue;
-    const int64_t chunk = kChunk / 64;
-    for (int64_t t0 = 0; t0 < n_traj; t0 += chunk) {
-        const int64_t c = std::min(chunk, n_traj - t0);
-        const dim3 grid(grid_of(c * L, block)), blk(block);
-        T* xc = xi + t0 * ta.n_wp;
-        int32_t* ic = iters ? iters + t0 : iters;
-        T* fc = info ? info + t0 : info;
-#define KIN_TRT_LAUNCH_L(MA, LL)                                                                                     \
-        hipLaunchKernelGGL((k_traj_tree<T, MA, LL>), grid, blk, lds, st, parts, n_parts, ndof, boxes, a, ta, dof, minvT, \
-                           xc, ldx, c, ic, fc, ldi)
-#define KIN_TRT_LAUNCH(MA)                        \
-        switch (L) {                              \
-        case 8: KIN_TRT_LAUNCH_L(MA, 8); break;   \
-        case 16: KIN_TRT_LAUNCH_L(MA, 16); break; \
-        case 32: KIN_TRT_LAUNCH_L(MA, 32); break; \
-        default: KIN_TRT_LAUNCH_L(MA, 64); break; \
-        }
-        switch (maxA) {
-        case 8: KIN_TRT_LAUNCH(8); break;
-        case 16: KIN_TRT_LAUNCH(16); break;
-        default: return hipErrorInvalidValue;  // (kin_traj_opt_tree_batch refuses longer chains)
-        }
-#undef KIN_TRT_LAUNCH
-#undef KIN_TRT_LAUNCH_L
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-}
-
-#define KIN_INSTANTIATE(T)                                                                                       \
-    template hipError_t launch_traj<T>(const KProg<T>&, const KStep<T>*, const KSphere<T>*, const KBox<T>*,      \
-                                       const LaunchGeom&, const CollArgs&, const TrajArgs&, const TrajDof&,     \
-                                       const T*, T*, int64_t, int64_t, int32_t*, T*, int64_t, hipStream_t);    \
-    template hipError_t launch_traj_pose<T>(const KProg<T>&, const KStep<T>*, const KSphere<T>*, const KBox<T>*, \
-                                            const LaunchGeom&, const CollArgs&, const TrajArgs&, const TrajDof&, \
-                                            const TrajPose<T>&, const T*, const T*, int64_t, T*, int64_t,       \
-                                            int64_t, int32_t*, T*, int64_t, hipStream_t);               \
-    template hipError_t launch_traj_tree<T>(const TrajPart<T>*, int, int, int, const KBox<T>*, const CollArgs&,  \
-                                            const TrajArgs&, const TrajDof&, const T*, T*, int64_t, int64_t,     \
-                                            int32_t*, T*, int64_t, hipStream_t);
-KIN_INSTANTIATE(float)
-KIN_INSTANTIATE(double)
+template hipError_t launch_traj<float>(const TrajLaunch<float>&, const KBox<float>*, const CollArgs&, const TrajArgs&,
+                                       const TrajDof&, const float*, float*, int64_t, int64_t, int32_t*, float*, int64_t,
+                                       hipStream_t);
+template hipError_t launch_traj<double>(const TrajLaunch<double>&, const KBox<double>*, const CollArgs&, const TrajArgs&,
+                                        const TrajDof&, const double*, double*, int64_t, int64_t, int32_t*, double*,
+                                        int64_t, hipStream_t);
 
 }  // namespace kinhip

@@ -1,6 +1,5 @@
-// kinhip_traj_dev.h -- device body of k_traj: batched trajectory optimisation (kin_traj_opt_batch).
-// Included by kinhip_traj.hip only (no run-time specialisation: not part of the embedded sources).
-// gfx950 only.
+// kinhip_traj_dev.h -- traj_body, the one device body of k_traj (kin_traj_opt_batch), k_traj_pose (POSE) and k_traj_tree
+// (TREE).  Included by kinhip_traj.hip only (no run-time specialisation: not part of the embedded sources).  gfx950 only.
 //
 // Many independent trajectories of n_wp waypoints per launch, one lane per waypoint, each trajectory
 // in a wave segment of L = 8 / 16 / 32 / 64 lanes (the smallest L >= n_wp).  Per iteration a lane
@@ -14,6 +13,10 @@
 // target at one interior waypoint.  The walk of traj_penalty also yields the link's frame; the residual norms of
 // lane wp enter the merit; after the Minv g pass the segment's lanes each redo the walk at the broadcast x_wp and
 // solve the 6 x 6 system of the constrained update (traj_pose_newton).  No barrier and no LDS beyond POSE = false.
+//
+// TREE = true (kin_traj_opt_tree_batch, common bounds 8 and 16): the POSE = false loop with the sphere sum of the merit
+// and its half-gradient taken over every part of a multi-chain plan: a lane walks part after part in plan order, the
+// walk state of a part dead before the next one starts.  Always ND = kTrajNdLarge columns; ndof is a kernel argument.
 #pragma once
 #include "kinhip_coll_dev.h"
 #include "kinhip_ik_dev.h"  // rot_error (the POSE variant's rotation residual)
@@ -362,17 +365,19 @@ __device__ __forceinline__ void traj_pose_newton(const KProg<T>& P, const KStep<
     for (int k = 0; k < ND; ++k) u[k] *= (T)dof.iW[k];
 }
 
-template <typename T, int MAXA, int L, bool POSE = false>
+// P, S, sph: the chain (not TREE); tp, targets, ldt: POSE only; parts, n_parts, nd (q columns + base): TREE only
+template <typename T, int MAXA, int L, bool POSE = false, bool TREE = false>
 __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __restrict__ S,
                                           const KSphere<T>* __restrict__ sph, const KBox<T>* __restrict__ boxes,
                                           const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
                                           const T* __restrict__ minvT, T* __restrict__ xi, int64_t ldx, int64_t n_traj,
                                           int32_t* __restrict__ iters, T* __restrict__ info, int64_t ldi,
                                           unsigned char* smem, const TrajPose<T>* __restrict__ tp = nullptr,
-                                          const T* __restrict__ targets = nullptr, int64_t ldt = 0) {
-    constexpr int ND = TrajNd<MAXA>::v;
+                                          const T* __restrict__ targets = nullptr, int64_t ldt = 0,
+                                          const TrajPart<T>* __restrict__ parts = nullptr, int n_parts = 0, int nd = 0) {
+    constexpr int ND = TREE ? kTrajNdLarge : TrajNd<MAXA>::v;
     const int n_wp = ta.n_wp, ni = n_wp - 2;
-    const int ndof = P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
+    const int ndof = TREE ? nd : P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
     // LDS: [the union's boxes (as k_coll) | Minv^T, ni x ni | g, one row of ndof per lane]
     const bool use_lds = a.n_boxes <= kCollLdsBoxes;  // uniform
     const int box_bytes = use_lds ? a.n_boxes * (int)sizeof(KBox<T>) : 0;
@@ -433,6 +438,26 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
             traj_pose_norms(r, rpn, rrn);
             rpn = __shfl(rpn, tp->wp, L);  // lane wp of the segment holds the constrained waypoint
             rrn = __shfl(rrn, tp->wp, L);
+        } else if constexpr (TREE) {
+            // every part's steps are padded to MAXA in the table: the unrolled walk never reads past a staged program; each
+            // part recomputes the base frame and the spheres (root-frame ones too) are disjoint: nothing is counted twice
+            pen = T(0);
+            dmin = T(INFINITY);
+#pragma unroll
+            for (int k = 0; k < ND; ++k) gn[k] = T(0);
+            for (int p = 0; p < n_parts; ++p) {  // (uniform; the chain inside stays unrolled)
+                const TrajPart<T>& pt = parts[p];
+                const char* tab = reinterpret_cast<const char*>(parts);  // (offsets from the kernel argument: global loads)
+                const KStep<T>* __restrict__ Sp = reinterpret_cast<const KStep<T>*>(tab + pt.steps_off);
+                const KSphere<T>* __restrict__ sp = reinterpret_cast<const KSphere<T>*>(tab + pt.sph_off);
+                T gp[ND], penp, dminp;
+                traj_penalty<T, MAXA, ND>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior,
+                                          trunc, weight, gp, penp, dminp);
+#pragma unroll
+                for (int k = 0; k < ND; ++k) gn[k] += gp[k];
+                pen += penp;
+                dmin = fmin(dmin, dminp);
+            }
         } else {
             traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc,
                                       weight, gn, pen, dmin);
@@ -547,165 +572,6 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                 info[4 * ldi + t] = rpc;
                 info[5 * ldi + t] = rrc;
             }
-        }
-    }
-}
-
-// ---- k_traj_tree (kin_traj_opt_tree_batch): the spheres of a plan with several sphere chains ----
-// traj_body's lane layout, line search, Minv g pass and result writes (POSE = false) with the sphere sum of the merit
-// and its half-gradient taken over every part of the plan.  Per iteration a lane walks part after part in plan order:
-// traj_penalty on the part's program header, steps and spheres, all in the part table and read by the uniform loop
-// index;
-// the part's g and pen are added to the running sums, dmin enters the running minimum.  The walk state of a part is
-// dead before the next one starts.  Every part's steps are padded to MAXA in the table (kin_coll_plan_create), so the
-// unrolled walk never reads past a staged program; each part recomputes the base frame, and the spheres (root-frame
-// ones included) are disjoint between parts, so nothing is counted twice.  Always ND = kTrajNdLarge columns.
-template <typename T, int MAXA, int L>
-__device__ __forceinline__ void traj_tree_body(const TrajPart<T>* __restrict__ parts, int n_parts, int ndof,
-                                               const KBox<T>* __restrict__ boxes, const CollArgs& a, const TrajArgs& ta,
-                                               const TrajDof& dof, const T* __restrict__ minvT, T* __restrict__ xi,
-                                               int64_t ldx, int64_t n_traj, int32_t* __restrict__ iters,
-                                               T* __restrict__ info, int64_t ldi, unsigned char* smem) {
-    constexpr int ND = kTrajNdLarge;
-    const int n_wp = ta.n_wp, ni = n_wp - 2;
-    // LDS as traj_body: [the union's boxes | Minv^T, ni x ni | g, one row of ndof per lane]
-    const bool use_lds = a.n_boxes <= kCollLdsBoxes;  // uniform
-    const int box_bytes = use_lds ? a.n_boxes * (int)sizeof(KBox<T>) : 0;
-    T* __restrict__ mt = reinterpret_cast<T*>(smem + box_bytes);
-    T* __restrict__ gl = mt + ni * ni;
-    if (use_lds) {
-        const int words = a.n_boxes * (int)(sizeof(KBox<T>) / 16);
-        for (int w = (int)threadIdx.x; w < words; w += (int)blockDim.x)
-            reinterpret_cast<uint4*>(smem)[w] = reinterpret_cast<const uint4*>(boxes)[w];
-    }
-    for (int k = (int)threadIdx.x; k < ni * ni; k += (int)blockDim.x) mt[k] = minvT[k];
-    __syncthreads();  // the only workgroup barrier (traj_body's)
-
-    const int64_t gt = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t t = gt / L;
-    const int w = (int)(gt % L);
-    if (__all(t >= n_traj)) return;
-    const bool valid = t < n_traj && w < n_wp;
-    const bool interior = valid && w >= 1 && w <= n_wp - 2;
-    const uint32_t off = valid ? (uint32_t)((t * n_wp + w) * (int64_t)sizeof(T)) : 0u;
-    const KAabb<T>* aabb = reinterpret_cast<const KAabb<T>*>(boxes + a.n_boxes);
-
-    const T trunc = (T)(ta.margin + ta.band), weight = (T)ta.weight;
-    const T feas_d = (T)(ta.margin - ta.feas), ftol = (T)ta.ftol, max_step = (T)ta.max_step;
-
-    T x[ND], xn[ND], g[ND], gn[ND];
-#pragma unroll
-    for (int k = 0; k < ND; ++k) {
-        x[k] = T(0);
-        if (k < ndof && valid) x[k] = ld_soa(xi, k, ldx, off);
-        xn[k] = x[k];
-        g[k] = T(0);
-    }
-    T alpha = T(1), f = T(0), fsm = T(0), dcur = T(INFINITY);
-    bool fin = !(t < n_traj);
-    int it_done = ta.max_iters + 1, nacc = 0;
-    const int lane = (int)threadIdx.x;
-    const int seg0 = lane - w;
-    const int wi = min(max(w - 1, 0), ni - 1);
-
-    for (int it = 0;; ++it) {
-        // ---- the merit and its half-gradient at xn: part after part ----
-        T pen = T(0), dmin = T(INFINITY);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) gn[k] = T(0);
-        for (int p = 0; p < n_parts; ++p) {  // (uniform; the chain inside stays unrolled)
-            const TrajPart<T>& pt = parts[p];
-            const char* tab = reinterpret_cast<const char*>(parts);  // (offsets from the kernel argument: global loads)
-            const KStep<T>* __restrict__ S = reinterpret_cast<const KStep<T>*>(tab + pt.steps_off);
-            const KSphere<T>* __restrict__ sph = reinterpret_cast<const KSphere<T>*>(tab + pt.sph_off);
-            T gp[ND], penp, dminp;
-            traj_penalty<T, MAXA, ND>(pt.P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior,
-                                      trunc, weight, gp, penp, dminp);
-#pragma unroll
-            for (int k = 0; k < ND; ++k) gn[k] += gp[k];
-            pen += penp;
-            dmin = fmin(dmin, dminp);
-        }
-        T sm = T(0);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) {
-            if (k >= ndof) continue;  // uniform
-            const T xm = __shfl_up(xn[k], 1), xp = __shfl_down(xn[k], 1);
-            const T aw = interior ? (xm - T(2) * xn[k]) + xp : T(0);
-            const T am = __shfl_up(aw, 1), ap = __shfl_down(aw, 1);
-            const T ax = (am - T(2) * aw) + ap;
-            const T Wk = (T)dof.W[k];
-            gn[k] = interior ? fma(Wk, ax, gn[k]) : T(0);
-            sm = fma(Wk * aw, aw, sm);
-        }
-        const T fn = seg_sum<L>(sm + pen);
-        const T smn = seg_sum<L>(sm);
-        const T dn = seg_min<L>(dmin);
-        // ---- accept / reject (per segment) ----
-        const bool live = !fin;
-        const bool acc = it == 0 ? true : (live && fn <= f);
-        const bool rej = it > 0 && live && !acc;
-        const bool done = it > 0 && acc && (f - fn < ftol) && (dn >= feas_d);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) {
-            x[k] = acc ? xn[k] : x[k];
-            g[k] = acc ? gn[k] : g[k];
-        }
-        f = acc ? fn : f;
-        fsm = acc ? smn : fsm;
-        dcur = acc ? dn : dcur;
-        if (it > 0) {
-            nacc += acc ? 1 : 0;
-            alpha = acc ? fmin(T(1), T(2) * alpha) : (rej ? T(0.25) * alpha : alpha);
-            fin = fin || done || (rej && alpha < T(1e-6));
-            it_done = done ? it : it_done;
-        }
-        if (it >= ta.max_iters || __all(fin)) break;
-        // ---- covariant step: -alpha W^-1 Minv g over the interior waypoints, through LDS ----
-#pragma unroll
-        for (int k = 0; k < ND; ++k)
-            if (k < ndof) gl[lane * ndof + k] = g[k];
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        T st[ND];
-#pragma unroll
-        for (int k = 0; k < ND; ++k) st[k] = T(0);
-        for (int v = 0; v < ni; ++v) {
-            const T mv = mt[v * ni + wi];
-            const T* __restrict__ gr = gl + (seg0 + 1 + v) * ndof;
-#pragma unroll
-            for (int k = 0; k < ND; ++k)
-                if (k < ndof) st[k] = fma(mv, gr[k], st[k]);
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        T mx = T(0);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) {
-            st[k] = interior && k < ndof ? -(alpha * (st[k] * (T)dof.iW[k])) : T(0);
-            mx = fmax(mx, fabs(st[k]));
-        }
-        mx = seg_max<L>(mx);
-        const T scale = mx > max_step ? max_step / mx : T(1);
-#pragma unroll
-        for (int k = 0; k < ND; ++k) {
-            const T c = fmin(fmax(x[k] + st[k] * scale, (T)dof.lo[k]), (T)dof.hi[k]);
-            xn[k] = (interior && !fin) ? c : x[k];
-        }
-    }
-    // ---- results: interior waypoints only ----
-    if (interior) {
-#pragma unroll
-        for (int k = 0; k < ND; ++k)
-            if (k < ndof) st_soa(xi, k, ldx, off, x[k]);
-    }
-    if (valid && w == 0) {
-        if (iters) iters[t] = it_done;
-        if (info) {
-            info[t] = f;
-            info[ldi + t] = fsm;
-            info[2 * ldi + t] = dcur;
-            info[3 * ldi + t] = (T)nacc;
         }
     }
 }

@@ -155,6 +155,51 @@ CollArgs traj_coll_args(const kin_sdf* sdf) {
                     {sdf->bh[0], sdf->bh[1], sdf->bh[2]}};
 }
 
+// the plan checks of every entry point; one_chain: kin_traj_opt_batch and kin_traj_opt_pose_batch refuse a plan with parts
+int traj_check_plan(const Bad& bad, const kin_plan* p, const kin_sdf* sdf, bool one_chain) {
+    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
+    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
+    if (one_chain && !p->parts.empty())
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off several chains (one sphere group only)");
+    if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
+    return KIN_OK;
+}
+
+// every entry point's tail: the arrays, then launch_traj (k_traj_tree for a plan with parts, k_traj_pose with pose, else k_traj)
+int traj_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+             const kin_traj_pose_params* pose, const void* targets, int64_t ldt, void* xi, int64_t ldx, int64_t n_traj,
+             int32_t* iters, void* info, int64_t ldi, void* stream) {
+    const void* minv = nullptr;
+    if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
+    if (n_traj == 0) return KIN_OK;
+    const bool tree = !p->parts.empty();
+    const hipError_t e = by_dtype(p->dtype, [&](auto t) {
+        using T = decltype(t);
+        const KProg<T>& P = p->prog<T>();
+        TrajPose<T> tp{};
+        if (pose) {
+            const kin_plan::PoseLink& pl = p->pose_links[0];  // constraint i refers to pose link i
+            to_row12<T>(pl.X, tp.X);
+            tp.nu = (T)pose->weight;
+            tp.damp = (T)pose->damp;
+            tp.tol_pos = (T)pose->tol_pos;
+            tp.tol_rot = (T)pose->tol_rot;
+            tp.step = pl.step;
+            tp.wp = pose->wp[0];
+            tp.with_rot = pose->with_rot[0];
+        }
+        // the chain, its bound and ndof (tree: the common bound, the plan's q columns), the pose arguments, the part table
+        TrajLaunch<T> d{&P, p->steps<T>(), p->sph<T>(), tree ? p->traj_tree_maxA : p->geom.maxA,
+                        tree ? p->nqcols : P.n_jac + ((P.flags & PF_BASE) ? 3 : 0), pose ? &tp : nullptr, (const T*)targets, ldt,
+                        tree ? (const TrajPart<T>*)p->d_traj_parts : nullptr, (int)p->parts.size()};
+        return launch_traj<T>(d, sdf->boxes<T>(), traj_coll_args(sdf), traj_args(prm), traj_dof(p, prm->dof_weights),
+                              (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
+    });
+    if (e != hipSuccess)
+        return set_error(KIN_E_DEVICE, std::string(tree ? "k_traj_tree launch: " : "k_traj launch: ") + hipGetErrorString(e));
+    return KIN_OK;
+}
+
 // kin_traj_opt_batch (pose == null) and kin_traj_opt_pose_batch; fn names the entry point in the messages
 int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
              const kin_traj_pose_params* pose, bool with_pose, const void* targets, int64_t ldt, void* xi, int64_t ldx,
@@ -176,11 +221,7 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
         if (!(pose->damp >= 0) || !std::isfinite(pose->damp)) return bad(KIN_E_INVALID, "damp must be finite and >= 0");
         if (n_traj > 0 && (!targets || ldt < n_traj)) return bad(KIN_E_INVALID, "bad targets / ldt (ldt >= n_traj)");
     }
-    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
-    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
-    if (!p->parts.empty())
-        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off several chains (one sphere group only)");
-    if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
+    if (const int rc = traj_check_plan(bad, p, sdf, true)) return rc;
     if (p->geom.maxA > kTrajMaxChain)
         return bad(KIN_E_UNSUPPORTED, "the sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
     if (with_pose && p->pose_links.empty())
@@ -190,69 +231,10 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
     const int nd_max = p->geom.maxA <= 8 ? kTrajNdSmall : kTrajNdLarge;
     if (p->nqcols > nd_max)
         return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(nd_max) + " q columns (+ base) for this chain");
-    const void* minv = nullptr;
-    if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
-    if (n_traj == 0) return KIN_OK;
-
-    const TrajDof dof = traj_dof(p, prm->dof_weights);
-    const TrajArgs ta = traj_args(prm);
-    const CollArgs ca = traj_coll_args(sdf);
-    const hipError_t e = by_dtype(p->dtype, [&](auto t) {
-        using T = decltype(t);
-        if (!with_pose)
-            return launch_traj<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof,
-                                  (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
-        const kin_plan::PoseLink& pl = p->pose_links[0];  // constraint i refers to pose link i
-        TrajPose<T> tp{};
-        to_row12<T>(pl.X, tp.X);
-        tp.nu = (T)pose->weight;
-        tp.damp = (T)pose->damp;
-        tp.tol_pos = (T)pose->tol_pos;
-        tp.tol_rot = (T)pose->tol_rot;
-        tp.step = pl.step;
-        tp.wp = pose->wp[0];
-        tp.with_rot = pose->with_rot[0];
-        return launch_traj_pose<T>(p->prog<T>(), p->steps<T>(), p->sph<T>(), sdf->boxes<T>(), p->geom, ca, ta, dof, tp,
-                                   (const T*)minv, (const T*)targets, ldt, (T*)xi, ldx, n_traj, iters, (T*)info, ldi,
-                                   (hipStream_t)stream);
-    });
-    if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj launch: ") + hipGetErrorString(e));
-    return KIN_OK;
+    return traj_run(bad, fn, p, sdf, prm, with_pose ? pose : nullptr, targets, ldt, xi, ldx, n_traj, iters, info, ldi,
+                    stream);
 }
 
-// kin_traj_opt_tree_batch: a single-chain plan runs kin_traj_opt_batch's own path (the same k_traj instantiation)
-int traj_opt_tree(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
-                  int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
-    const std::string fn = "kin_traj_opt_tree_batch";
-    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
-    if (const int rc = traj_check_params(bad, prm)) return rc;
-    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
-    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
-    if (p->parts.empty())
-        return traj_opt(fn, p, sdf, prm, nullptr, false, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
-    if (sdf->attached) return bad(KIN_E_UNSUPPORTED, "the kin_sdf is attached to a scene (a static union only)");
-    if ((int)p->parts.size() > kTrajMaxParts)
-        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
-                                          " chains (parts)");
-    for (const auto& s : p->parts)
-        if (s->geom.maxA > kTrajMaxChain)
-            return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
-    if (p->nqcols > kTrajNdLarge)
-        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
-    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
-    const void* minv = nullptr;
-    if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
-    if (n_traj == 0) return KIN_OK;
-    const TrajDof dof = traj_dof(p, prm->dof_weights);
-    const hipError_t e = by_dtype(p->dtype, [&](auto t) {
-        using T = decltype(t);
-        return launch_traj_tree<T>((const TrajPart<T>*)p->d_traj_parts, (int)p->parts.size(), p->traj_tree_maxA,
-                                   p->nqcols, sdf->boxes<T>(), traj_coll_args(sdf), traj_args(prm), dof, (const T*)minv,
-                                   (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
-    });
-    if (e != hipSuccess) return set_error(KIN_E_DEVICE, std::string("k_traj_tree launch: ") + hipGetErrorString(e));
-    return KIN_OK;
-}
 }  // namespace
 
 int kin_traj_opt_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
@@ -268,9 +250,25 @@ int kin_traj_opt_pose_batch(const kin_plan* p, const kin_sdf* sdf, const kin_tra
                     stream);
 }
 
+// a single-chain plan runs kin_traj_opt_batch's own path (the same k_traj instantiation)
 int kin_traj_opt_tree_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, void* xi, int64_t ldx,
                             int64_t n_traj, int32_t* iters, void* info, int64_t ldi, void* stream) {
-    return traj_opt_tree(p, sdf, prm, xi, ldx, n_traj, iters, info, ldi, stream);
+    const std::string fn = "kin_traj_opt_tree_batch";
+    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
+    if (const int rc = traj_check_params(bad, prm)) return rc;
+    if (const int rc = traj_check_plan(bad, p, sdf, false)) return rc;
+    if (p->parts.empty())  // (its remaining checks; the ones above pass again)
+        return traj_opt(fn, p, sdf, prm, nullptr, false, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
+    if ((int)p->parts.size() > kTrajMaxParts)
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
+                                          " chains (parts)");
+    for (const auto& s : p->parts)
+        if (s->geom.maxA > kTrajMaxChain)
+            return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
+    if (p->nqcols > kTrajNdLarge)
+        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
+    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
+    return traj_run(bad, fn, p, sdf, prm, nullptr, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
 }
 
 }  // extern "C"
