@@ -525,7 +525,7 @@ KINHIP_API int kin_pose_const_batch(const kin_plan* p, const void* target, int64
  * problem to SLSQP); its fp64 iterates are pinned against a CPU restatement (tests/trajopt_ref.py).
  * Limits: 3 <= n_wp <= 64; a plan of kin_coll_plan_create whose spheres are one group (one chain) of at most
  * 16 steps, with at most 12 q columns (+ base) for chains of <= 8 steps, 20 otherwise; a static kin_sdf
- * (KIN_E_UNSUPPORTED beyond).  kin_plan_specialize leaves this call on its generic kernel. */
+ * (KIN_E_UNSUPPORTED beyond; a union attached to a scene: kin_traj_opt_scene_batch).  kin_plan_specialize leaves this call on its generic kernel. */
 typedef struct kin_traj_params {
     int32_t n_wp, max_iters;
     double margin, band, weight, feas;   /* meaning as kin_ik_coll_params */
@@ -589,10 +589,28 @@ KINHIP_API int kin_traj_opt_pose_batch(const kin_plan* traj_plan, const kin_sdf*
  * Limits (KIN_E_UNSUPPORTED): at most 4 parts; every part's chain at most 16 steps; at most 20 q columns (+ base)
  * whatever the chain bounds; a static kin_sdf; 3 <= n_wp <= 64.
  * Not covered: pose constraints on a multi-chain plan (kin_traj_opt_pose_batch keeps refusing such plans, as does
- * kin_traj_opt_batch) and unions attached to a scene. */
+ * kin_traj_opt_batch).  Unions attached to a scene: kin_traj_opt_scene_batch (this call refuses them). */
 KINHIP_API int kin_traj_opt_tree_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
                                        void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
                                        void* stream);
+
+/* kin_traj_opt_tree_batch against boxes attached to a scene mechanism (kin_sdf_create_attached; UnionSDF(fridge) of
+ * fridge_demo.jl), every waypoint of every trajectory with its own scene state: a door that swings while the robot
+ * moves, or a different door angle per trajectory, is one launch (k_traj_scene).  Merit, half-gradient, line search,
+ * limits clamp, iters and the four info rows are kin_traj_opt_batch's; a sphere's distance and SDF gradient at
+ * waypoint w come from the union at that waypoint's scene state (kin_coll_batch_scene's distance), and info row 2 is
+ * the minimum over the interior waypoints, each against its own state.  The scene is data: never differentiated.
+ *   scene_q [n_scene_cols][lds]  the scene joint values (+ base x, y, theta), sample t*n_wp + w as xi's columns;
+ *                                lds = 0: one set of values for the whole launch; else lds >= n_traj * n_wp
+ * Takes single-chain and multi-part plans of kin_coll_plan_create.  A static kin_sdf is KIN_E_INVALID (use
+ * kin_traj_opt_tree_batch).  Limits (KIN_E_UNSUPPORTED): kin_traj_opt_tree_batch's (at most 4 parts, 16 steps per
+ * part, 20 q columns (+ base), 3 <= n_wp <= 64) and a union of at most 2 moving groups (the fridge: its base and its
+ * door).  Not covered: pose constraints with a scene; kin_plan_specialize_scene leaves this call on its generic
+ * kernel.  Capture and the metric table as kin_traj_opt_batch (the same table).  Pinned against
+ * tests/trajopt_scene_ref.py on tests/trajopt_scene_cases.py. */
+KINHIP_API int kin_traj_opt_scene_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
+                                        const void* scene_q, int64_t lds, void* xi, int64_t ldx, int64_t n_traj,
+                                        int32_t* iters, void* info, int64_t ldi, void* stream);
 /* the chain programs (parts) of a plan: 1 unless kin_coll_plan_create found spheres on several chains; the
  * compiled chain bound (4 / 8 / 12 / 16 / 32) of part 0 .. count-1 (a single-chain plan: kin_plan_chain_bound) */
 KINHIP_API int kin_plan_part_count(const kin_plan* p, int32_t* out);

@@ -230,15 +230,19 @@ int kin_plan_specialized(const kin_plan* p, uint32_t* kernels) {
 }
 
 namespace {
-// The part table of k_traj_tree (kin_traj_opt_tree_batch) for a multi-chain plan within its limits, one device
+// The part table of k_traj_tree (kin_traj_opt_tree_batch) for a multi-chain plan within its limits -- and, with one
+// entry, of a single-chain plan (kin_traj_opt_scene_batch runs every plan through the part loop) -- one device
 // allocation [TrajPart<T>[n_parts] | steps | spheres]: the parts' program headers, copies of their phase-A steps
 // padded with identity steps to the common bound (so that the kernel's unrolled walk stays inside every staged
 // program) and copies of their sphere tables.  What kin_coll_batch launches for a part (its own steps at its own
 // bound) is untouched.
 int upload_traj_parts(kin_plan& top, const std::string& fn) {
-    const size_t np = top.parts.size();
+    std::vector<const kin_plan*> parts;
+    for (const auto& s : top.parts) parts.push_back(s.get());
+    if (parts.empty()) parts.push_back(&top);
+    const size_t np = parts.size();
     int maxA = 0;
-    for (const auto& s : top.parts) maxA = std::max(maxA, s->geom.maxA);
+    for (const kin_plan* s : parts) maxA = std::max(maxA, s->geom.maxA);
     if (np > (size_t)kTrajMaxParts || maxA > kTrajMaxChain) return KIN_OK;  // (refused at the call)
     const int bound = maxA <= 8 ? 8 : 16;
     return by_dtype(top.dtype, [&](auto t) -> int {
@@ -248,7 +252,7 @@ int upload_traj_parts(kin_plan& top, const std::string& fn) {
         std::vector<size_t> sph_off(np);
         for (size_t k = 0; k < np; ++k) {
             sph_off[k] = bytes;
-            bytes += top.parts[k]->h_sph.size();
+            bytes += parts[k]->h_sph.size();
         }
         std::vector<unsigned char> h(bytes, 0);
         KStep<T> pad;
@@ -261,7 +265,7 @@ int upload_traj_parts(kin_plan& top, const std::string& fn) {
         pad.qcol = pad.out = pad.save = -1;
         pad.load = LOAD_NONE;
         for (size_t k = 0; k < np; ++k) {
-            const kin_plan& s = *top.parts[k];
+            const kin_plan& s = *parts[k];
             TrajPart<T>* tp = reinterpret_cast<TrajPart<T>*>(h.data()) + k;
             KStep<T>* hs = reinterpret_cast<KStep<T>*>(h.data() + steps_off) + k * bound;
             tp->P = s.prog<T>();
@@ -357,6 +361,7 @@ int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose,
     std::unique_ptr<kin_plan> top;
     if (parts.size() == 1) {
         top = std::move(parts[0]);
+        if (const int rc = upload_traj_parts(*top, fn)) return rc;
     } else {
         top = std::make_unique<kin_plan>();
         top->dtype = parts[0]->dtype;

@@ -184,6 +184,9 @@ struct TrajPose {
 // copy of its spheres, addressed by byte offsets from the table's start (offsets from the kernel argument, not
 // pointers read from memory: the kernel's loads stay global, tests/test_isa.py).
 constexpr int kTrajMaxParts = 4;
+// k_traj_scene (kin_traj_opt_scene_batch): k_traj_tree against a union attached to a scene of at most this many
+// moving groups (the lane's group frames stay in registers over the descent, 12 per group)
+constexpr int kTrajSceneGroups = 2;
 template <typename T>
 struct TrajPart {
     KProg<T> P;
@@ -203,7 +206,33 @@ struct TrajLaunch {
     int64_t ldt = 0;
     const TrajPart<T>* parts = nullptr;  // k_traj_tree (else null)
     int n_parts = 0;
+    // k_traj_scene (else null; with parts, a single-chain plan's one-entry table included): the union's scene tables
+    // and scene_q [cols][ld], sample t * n_wp + w = waypoint w of trajectory t (uniform: one set for the launch)
+    const SceneLaunch* scene = nullptr;
 };
+// one chunk of launch_traj's loop for k_traj_scene (kinhip_traj_scene.hip; called by launch_traj only)
+template <typename T>
+struct TrajSceneChunk {
+    dim3 grid, block;
+    size_t lds;
+    hipStream_t st;
+    const TrajPart<T>* parts;
+    int n_parts, ndof;
+    const KBox<T>* boxes;
+    const CollArgs* a;
+    const TrajArgs* ta;
+    const TrajDof* dof;
+    const T* minvT;
+    const SceneLaunch* scene;
+    int64_t sample0;  // the chunk's first sample of scene_q
+    T* xi;
+    int64_t ldx, n_traj;
+    int32_t* iters;
+    T* info;
+    int64_t ldi;
+};
+template <typename T>
+bool launch_traj_scene_chunk(int maxA, int L, const TrajSceneChunk<T>& k);
 // minv: (A_sub[I,I])^-1 of n_wp waypoints on the device, row-major (symmetric, so also its transpose)
 template <typename T>
 hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollArgs& a, const TrajArgs& ta,

@@ -17,6 +17,11 @@
 // TREE = true (kin_traj_opt_tree_batch, common bounds 8 and 16): the POSE = false loop with the sphere sum of the merit
 // and its half-gradient taken over every part of a multi-chain plan: a lane walks part after part in plan order, the
 // walk state of a part dead before the next one starts.  Always ND = kTrajNdLarge columns; ndof is a kernel argument.
+//
+// SCENE != 0 (kin_traj_opt_scene_batch, k_traj_scene in kinhip_traj_scene.hip; TREE only): the union's boxes are
+// attached to a scene mechanism of at most SCENE moving groups and every waypoint has its own scene state: the lane
+// forms its group frames once (scene_frames at its own sample offset, held in registers over the descent) and its
+// spheres go through scene_union instead of union_sdf.  The scene is data: nothing is differentiated through it.
 #pragma once
 #include "kinhip_coll_dev.h"
 #include "kinhip_ik_dev.h"  // rot_error (the POSE variant's rotation residual)
@@ -80,13 +85,14 @@ struct TrajFrameAt {
     }
 };
 
-template <typename T, int MAXA, int ND, typename Hook = TrajNoHook>
+template <typename T, int MAXA, int ND, typename Hook = TrajNoHook, int SCENE = 0>
 __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* __restrict__ S,
                                              const KSphere<T>* __restrict__ sph, const KBox<T>* __restrict__ boxes,
                                              const KAabb<T>* __restrict__ aabb, int na, int nb,
                                              const unsigned char* smem, bool use_lds, const T (&x)[ND], bool interior,
                                              T trunc, T weight, T (&g)[ND], T& pen, T& dmin,
-                                             Hook hook = Hook()) {  // (by value: a reference's temporary changed k_traj's code)
+                                             Hook hook = Hook(),  // (by value: a reference's temporary changed k_traj's code)
+                                             const SceneCtx<T, SCENE ? SCENE : 1>* sc = nullptr) {  // (SCENE != 0 only)
     const bool base = (P.flags & PF_BASE) != 0;
     T bx = T(0), by = T(0), bth = T(0);
     if (base) {
@@ -114,7 +120,8 @@ __device__ __forceinline__ void traj_penalty(const KProg<T>& P, const KStep<T>* 
         px[0] = fma(f.r[0], sp.c[0], fma(f.r[1], sp.c[1], fma(f.r[2], sp.c[2], f.t[0])));
         py[0] = fma(f.r[3], sp.c[0], fma(f.r[4], sp.c[1], fma(f.r[5], sp.c[2], f.t[1])));
         pz[0] = fma(f.r[6], sp.c[0], fma(f.r[7], sp.c[1], fma(f.r[8], sp.c[2], f.t[2])));
-        union_sdf<T, true, 1>(boxes, aabb, na, nb, px, py, pz, ds, gw, smem, use_lds);
+        if constexpr (SCENE != 0) scene_union<T, true, 1, SCENE>(*sc, boxes, aabb, px, py, pz, ds, gw, smem, use_lds);
+        else union_sdf<T, true, 1>(boxes, aabb, na, nb, px, py, pz, ds, gw, smem, use_lds);
         const T d = ds[0] - sp.r;
         const T r = interior ? weight * fmax(T(0), trunc - d) : T(0);
         dmin = interior ? fmin(dmin, d) : dmin;
@@ -365,8 +372,9 @@ __device__ __forceinline__ void traj_pose_newton(const KProg<T>& P, const KStep<
     for (int k = 0; k < ND; ++k) u[k] *= (T)dof.iW[k];
 }
 
-// P, S, sph: the chain (not TREE); tp, targets, ldt: POSE only; parts, n_parts, nd (q columns + base): TREE only
-template <typename T, int MAXA, int L, bool POSE = false, bool TREE = false>
+// P, S, sph: the chain (not TREE); tp, targets, ldt: POSE only; parts, n_parts, nd (q columns + base): TREE only;
+// sa: SCENE != 0 only (its q already at the launch chunk's first sample)
+template <typename T, int MAXA, int L, bool POSE = false, bool TREE = false, int SCENE = 0>
 __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __restrict__ S,
                                           const KSphere<T>* __restrict__ sph, const KBox<T>* __restrict__ boxes,
                                           const CollArgs& a, const TrajArgs& ta, const TrajDof& dof,
@@ -374,7 +382,9 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                                           int32_t* __restrict__ iters, T* __restrict__ info, int64_t ldi,
                                           unsigned char* smem, const TrajPose<T>* __restrict__ tp = nullptr,
                                           const T* __restrict__ targets = nullptr, int64_t ldt = 0,
-                                          const TrajPart<T>* __restrict__ parts = nullptr, int n_parts = 0, int nd = 0) {
+                                          const TrajPart<T>* __restrict__ parts = nullptr, int n_parts = 0, int nd = 0,
+                                          const SceneArgs<T>* sa = nullptr) {
+    static_assert(SCENE == 0 || (TREE && !POSE), "the scene variant is the part loop's");
     constexpr int ND = TREE ? kTrajNdLarge : TrajNd<MAXA>::v;
     const int n_wp = ta.n_wp, ni = n_wp - 2;
     const int ndof = TREE ? nd : P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
@@ -399,6 +409,10 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
     const bool interior = valid && w >= 1 && w <= n_wp - 2;
     const uint32_t off = valid ? (uint32_t)((t * n_wp + w) * (int64_t)sizeof(T)) : 0u;
     const KAabb<T>* aabb = reinterpret_cast<const KAabb<T>*>(boxes + a.n_boxes);
+    // SCENE: this waypoint's group frames, once (the scene does not change during the solve); lanes without a
+    // waypoint take sample 0 of the chunk (off = 0: in range)
+    SceneCtx<T, SCENE ? SCENE : 1> sc;
+    if constexpr (SCENE != 0) scene_frames(sc, *sa, off);
 
     const T trunc = (T)(ta.margin + ta.band), weight = (T)ta.weight;
     const T feas_d = (T)(ta.margin - ta.feas), ftol = (T)ta.ftol, max_step = (T)ta.max_step;
@@ -451,8 +465,13 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                 const KStep<T>* __restrict__ Sp = reinterpret_cast<const KStep<T>*>(tab + pt.steps_off);
                 const KSphere<T>* __restrict__ sp = reinterpret_cast<const KSphere<T>*>(tab + pt.sph_off);
                 T gp[ND], penp, dminp;
-                traj_penalty<T, MAXA, ND>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior,
-                                          trunc, weight, gp, penp, dminp);
+                if constexpr (SCENE != 0)
+                    traj_penalty<T, MAXA, ND, TrajNoHook, SCENE>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem,
+                                                                 use_lds, xn, interior, trunc, weight, gp, penp, dminp,
+                                                                 TrajNoHook(), &sc);
+                else
+                    traj_penalty<T, MAXA, ND>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior,
+                                              trunc, weight, gp, penp, dminp);
 #pragma unroll
                 for (int k = 0; k < ND; ++k) gn[k] += gp[k];
                 pen += penp;

@@ -1,6 +1,7 @@
 // kinhip_trajopt.cpp -- C-ABI of the batched trajectory optimiser: kin_traj_opt_batch (k_traj,
 // kinhip_traj.hip), kin_traj_opt_pose_batch (its POSE variant: one pose link held at a waypoint),
-// kin_traj_opt_tree_batch (k_traj_tree: spheres on several chains) and their metric table.
+// kin_traj_opt_tree_batch (k_traj_tree: spheres on several chains), kin_traj_opt_scene_batch (k_traj_scene: the
+// union attached to a scene, one scene state per waypoint) and their metric table.
 //
 // Reference semantics restated here (host side):
 //   Objective's A_sub (finite-difference accelerations)    src/planning.jl:1-28
@@ -168,11 +169,11 @@ int traj_check_plan(const Bad& bad, const kin_plan* p, const kin_sdf* sdf, bool 
 // every entry point's tail: the arrays, then launch_traj (k_traj_tree for a plan with parts, k_traj_pose with pose, else k_traj)
 int traj_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
              const kin_traj_pose_params* pose, const void* targets, int64_t ldt, void* xi, int64_t ldx, int64_t n_traj,
-             int32_t* iters, void* info, int64_t ldi, void* stream) {
+             int32_t* iters, void* info, int64_t ldi, void* stream, const SceneLaunch* scene = nullptr) {
     const void* minv = nullptr;
     if (const int rc = traj_check_arrays(bad, fn, p, sdf, prm, xi, ldx, n_traj, info, ldi, stream, &minv)) return rc;
     if (n_traj == 0) return KIN_OK;
-    const bool tree = !p->parts.empty();
+    const bool tree = scene || !p->parts.empty();  // (the scene kernel: a single-chain plan's one-entry table)
     const hipError_t e = by_dtype(p->dtype, [&](auto t) {
         using T = decltype(t);
         const KProg<T>& P = p->prog<T>();
@@ -191,12 +192,14 @@ int traj_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin
         // the chain, its bound and ndof (tree: the common bound, the plan's q columns), the pose arguments, the part table
         TrajLaunch<T> d{&P, p->steps<T>(), p->sph<T>(), tree ? p->traj_tree_maxA : p->geom.maxA,
                         tree ? p->nqcols : P.n_jac + ((P.flags & PF_BASE) ? 3 : 0), pose ? &tp : nullptr, (const T*)targets, ldt,
-                        tree ? (const TrajPart<T>*)p->d_traj_parts : nullptr, (int)p->parts.size()};
+                        tree ? (const TrajPart<T>*)p->d_traj_parts : nullptr,
+                        tree ? std::max(1, (int)p->parts.size()) : 0, scene};
         return launch_traj<T>(d, sdf->boxes<T>(), traj_coll_args(sdf), traj_args(prm), traj_dof(p, prm->dof_weights),
                               (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
     });
     if (e != hipSuccess)
-        return set_error(KIN_E_DEVICE, std::string(tree ? "k_traj_tree launch: " : "k_traj launch: ") + hipGetErrorString(e));
+        return set_error(KIN_E_DEVICE, std::string(scene ? "k_traj_scene launch: " : tree ? "k_traj_tree launch: " : "k_traj launch: ") +
+                                           hipGetErrorString(e));
     return KIN_OK;
 }
 
@@ -269,6 +272,40 @@ int kin_traj_opt_tree_batch(const kin_plan* p, const kin_sdf* sdf, const kin_tra
         return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
     if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
     return traj_run(bad, fn, p, sdf, prm, nullptr, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
+}
+
+// k_traj_scene: every plan through the part loop (a single-chain plan's one-entry table), the union attached to a scene
+int kin_traj_opt_scene_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm, const void* scene_q,
+                             int64_t lds, void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
+                             void* stream) {
+    const std::string fn = "kin_traj_opt_scene_batch";
+    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
+    if (const int rc = traj_check_params(bad, prm)) return rc;
+    if (lds < 0) return bad(KIN_E_INVALID, "lds < 0");
+    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
+    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
+    if (!sdf->attached)
+        return bad(KIN_E_INVALID, "the kin_sdf is not attached to a scene (a static union: kin_traj_opt_tree_batch)");
+    if (sdf->n_groups > kTrajSceneGroups)
+        return bad(KIN_E_UNSUPPORTED, "the union has " + std::to_string(sdf->n_groups) + " moving groups (at most " +
+                                          std::to_string(kTrajSceneGroups) + " moving groups)");
+    if ((int)p->parts.size() > kTrajMaxParts)
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
+                                          " chains (parts)");
+    const auto chain_ok = [](const kin_plan& s) { return s.geom.maxA <= kTrajMaxChain; };
+    bool ok = p->parts.empty() ? chain_ok(*p) : true;
+    for (const auto& s : p->parts) ok = ok && chain_ok(*s);
+    if (!ok) return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
+    if (p->nqcols > kTrajNdLarge)
+        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
+    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
+    if (n_traj > 0 && n_traj <= (int64_t(1) << 40) / prm->n_wp && sdf->scene_cols > 0 &&
+        (!scene_q || (lds != 0 && lds < n_traj * prm->n_wp)))
+        return bad(KIN_E_INVALID, "bad scene_q / lds (lds = 0: one scene state, else lds >= n_traj * n_wp)");
+    const void* sc = p->dtype == KIN_F32 ? sdf->d_scene_f32 : sdf->d_scene_f64;
+    const SceneLaunch sl{sc, (const char*)sc + sdf->scene_steps_off, scene_q, lds, sdf->n_groups, sdf->scene_base_col,
+                         lds == 0 ? 1 : 0};
+    return traj_run(bad, fn, p, sdf, prm, nullptr, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream, &sl);
 }
 
 }  // extern "C"

@@ -753,6 +753,40 @@ function plan_trajectories_tree!(hm::HIPModel, sscc::Kinematics.SweptSphereColli
     Xi, iters, info
 end
 
+"""`plan_trajectories_scene!(hm, sscc, joints, sdf, scene_q, Xi, n_wp; ...)`: `plan_trajectories_tree!` against an
+attached `HIPSDF(scene, scene_joints)` (the reference's `UnionSDF(fridge)` of fridge_demo.jl) through
+kin_traj_opt_scene_batch: every waypoint of every trajectory has its own scene state, so a door that swings while the
+robot moves is one launch.  `scene_q`: the scene columns per row of Xi, a (size(Xi, 1), n_scene_cols) ROCMatrix, or one
+ROCVector for the whole launch.  The same arrays, keywords and results as `plan_trajectories!`; spheres on one chain or
+on several; unions of at most 2 moving groups (the fridge's base and its door).  The scene is data, not optimised."""
+function plan_trajectories_scene!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionChecker, joints::Vector{<:Joint},
+                                  sdf::HIPSDF, scene_q::Union{ROCMatrix{T},ROCVector{T}}, Xi::ROCMatrix{T},
+                                  n_wp::Integer; margin::Real=2e-2, band::Real=3e-2, weight::Real=10.0,
+                                  feas::Real=1e-3, ftol::Real=1e-6, max_step::Real=0.5, max_iters::Integer=200,
+                                  dof_weights::Union{Nothing,Vector{Float64}}=nothing) where {T}
+    sdf.attached || throw(ArgumentError("plan_trajectories_scene! needs an attached HIPSDF (else plan_trajectories_tree!)"))
+    N = size(Xi, 1)
+    N % n_wp == 0 || error("size(Xi, 1) must be a multiple of n_wp")
+    scene_q isa ROCMatrix && size(scene_q, 1) != N && error("scene_q must have one row per row of Xi")
+    n_traj = div(N, n_wp)
+    p = coll_plan!(hm, T, sscc, joints)
+    iters = ROCVector{Int32}(undef, n_traj)
+    info = ROCMatrix{T}(undef, n_traj, 4)
+    lds = scene_q isa ROCMatrix ? stride(scene_q, 2) : 0  # (N, cols) per waypoint, or one vector
+    dw = dof_weights === nothing ? Float64[] : dof_weights
+    GC.@preserve dw begin
+        prm = Ref(KinTrajParams(Int32(n_wp), Int32(max_iters), Float64(margin), Float64(band), Float64(weight),
+                                Float64(feas), Float64(ftol), Float64(max_step),
+                                dof_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(dw)))
+        check(ccall((:kin_traj_opt_scene_batch, libkinhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{KinTrajParams}, Ptr{T}, Int64, Ptr{T}, Int64, Int64, Ptr{Int32}, Ptr{T},
+                     Int64, Ptr{Cvoid}),
+                    p, sdf.handle, prm, pointer(scene_q), lds, pointer(Xi), stride(Xi, 2), n_traj, pointer(iters),
+                    pointer(info), n_traj, stream_ptr()))
+    end
+    Xi, iters, info
+end
+
 # --- a pose constraint at a waypoint on the batched path (kin_traj_plan_create, kin_traj_opt_pose_batch) ---
 
 struct KinTrajPoseParams

@@ -44,7 +44,7 @@ EXPORTS = [
     "kin_coll_batch_scene", "kin_plan_ik_sched_stats", "kin_plan_specialize_scene", "kin_ik_coll_batch_alt",
     "kin_traj_opt_batch", "kin_traj_metric_inverse", "kin_plan_chain_bound",
     "kin_traj_plan_create", "kin_traj_opt_pose_batch",
-    "kin_traj_opt_tree_batch", "kin_plan_part_count", "kin_plan_part_chain_bound",
+    "kin_traj_opt_tree_batch", "kin_plan_part_count", "kin_plan_part_chain_bound", "kin_traj_opt_scene_batch",
 ]
 
 
@@ -169,6 +169,7 @@ def lib():
         "kin_traj_plan_create": ([P, P, I32, P, P], C.c_int),
         "kin_traj_opt_pose_batch": ([P, P, P, P, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_traj_opt_tree_batch": ([P, P, P, P, I64, I64, P, P, I64, P], C.c_int),
+        "kin_traj_opt_scene_batch": ([P, P, P, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_plan_part_count": ([P, P], C.c_int),
         "kin_plan_part_chain_bound": ([P, I32, P], C.c_int),
     }

@@ -24,7 +24,9 @@ covariant projected gradient on the smoothness objective plus sphere-clearance p
 different solver from SLSQP, see include/kinhip.h).  With one ``PoseConstraint`` of one link
 (``pose_link=`` ...) the same kernel's constrained variant runs (``kin_traj_opt_pose_batch``): the
 link is held at a target pose at one interior waypoint.  A checker whose spheres hang off several chains
-(two arms) runs ``kin_traj_opt_tree_batch`` (``traj_opt_tree_batch``; no pose constraint there).
+(two arms) runs ``kin_traj_opt_tree_batch`` (``traj_opt_tree_batch``; no pose constraint there).  Against an
+``AttachedUnionSDF`` (boxes on a moving scene, e.g. the fridge's door) ``kin_traj_opt_scene_batch`` runs
+(``traj_opt_scene_batch``): every waypoint of every trajectory has its own scene state `scene_q`.
 """
 from __future__ import annotations
 
@@ -35,7 +37,7 @@ import numpy as np
 import torch
 
 from . import _lib as K
-from .collision import SweptSphereCollisionChecker, UnionSDF
+from .collision import AttachedUnionSDF, SweptSphereCollisionChecker, UnionSDF, _plan_device
 from .mechanism import Link, Mechanism, _device, _same_device
 
 _DT = {torch.float32: K.KIN_F32, torch.float64: K.KIN_F64}
@@ -242,6 +244,53 @@ def traj_opt_tree_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, margin=
                      max_iters, dof_weights, iters, info, stream)
 
 
+def _scene_columns(plan, sdf, scene_q, X, n_traj, n_wp):
+    """`scene_q` of ``traj_opt_scene_batch`` -> (tensor whose storage the call reads, lds).  (n_scene_cols,): one
+    state for the launch (lds = 0); (n_scene_cols, n_traj): one per trajectory, expanded over its waypoints;
+    (n_scene_cols, n_traj * n_wp): one per waypoint, column t * n_wp + w."""
+    if not isinstance(scene_q, torch.Tensor):
+        raise ValueError("an AttachedUnionSDF needs scene_q (its scene joint values) as a tensor")
+    if scene_q.dtype != plan.dtype:
+        raise ValueError("scene_q must have the plan dtype")
+    _same_device(scene_q, X, "scene_q")
+    nc = sdf.n_scene_cols
+    if scene_q.dim() == 1:
+        if scene_q.shape[0] != nc or not scene_q.is_contiguous():
+            raise ValueError(f"scene_q must hold {nc} values")
+        return scene_q, 0
+    if scene_q.dim() == 2 and scene_q.shape == (nc, n_traj) and n_wp != 1:
+        scene_q = scene_q.repeat_interleave(n_wp, dim=1)
+    if scene_q.dim() != 2 or scene_q.shape != (nc, n_traj * n_wp) or (scene_q.numel() and scene_q.stride(1) != 1):
+        raise ValueError(f"scene_q must be ({nc},), ({nc}, n_traj) or ({nc}, n_traj * n_wp) with unit sample stride")
+    return scene_q, max(scene_q.stride(0), n_traj * n_wp)
+
+
+def traj_opt_scene_batch(plan, sdf: AttachedUnionSDF, X: torch.Tensor, n_wp: int, scene_q: torch.Tensor, margin=2e-2,
+                         band=3e-2, weight=10.0, feas=1e-3, ftol=1e-6, max_step=0.5, max_iters=200, dof_weights=None,
+                         iters=None, info=None, stream=None):
+    """kin_traj_opt_scene_batch: ``traj_opt_tree_batch`` (single-chain and multi-part ``CollisionPlan``s alike)
+    against an ``AttachedUnionSDF`` of at most 2 moving groups, every waypoint with its own scene state.  `scene_q`
+    holds the union's scene columns (its joints, then the scene's planar base x, y, theta): (n_scene_cols,) for the
+    whole launch, (n_scene_cols, n_traj) per trajectory, or (n_scene_cols, n_traj * n_wp) per waypoint (column
+    t * n_wp + w, as X) -- a door that swings while the robot moves.  The scene is data, not optimised.  The same
+    arrays and results as ``traj_opt_batch``; info[2] is each interior waypoint's clearance at its own scene state
+    (``CollisionPlan.run(sdf, X, scene_q=...)``)."""
+    if not isinstance(sdf, AttachedUnionSDF):
+        raise TypeError("traj_opt_scene_batch needs an AttachedUnionSDF (a static UnionSDF: traj_opt_tree_batch)")
+    if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
+            or X.shape[1] % int(n_wp) != 0):
+        raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
+    _plan_device(plan, X)
+    _plan_device(sdf, X)
+    with torch.cuda.stream(stream or torch.cuda.current_stream(X.device)):   # (the per-trajectory form is expanded)
+        sq, lds = _scene_columns(plan, sdf, scene_q, X, X.shape[1] // int(n_wp), int(n_wp))
+
+    def entry(ph, sh, prm, *rest):
+        return K.lib().kin_traj_opt_scene_batch(ph, sh, prm, sq.data_ptr() if sq.numel() else None, lds, *rest)
+    return _traj_opt(entry, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step, max_iters, dof_weights,
+                     iters, info, stream)
+
+
 def _traj_opt(entry, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step, max_iters, dof_weights, iters,
               info, stream):
     if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
@@ -309,7 +358,7 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
                       margin=2e-2, band=3e-2, weight=10.0, max_iters=200, dtype=torch.float64, X0=None, stream=None,
                       feas=1e-3, ftol=1e-6, max_step=0.5, dof_weights=None, plan=None, check_ends=True,
                       pose_link=None, pose_wp=None, pose_targets=None, pose_with_rot=True, pose_weight=10.0,
-                      pose_tol=1e-3):
+                      pose_tol=1e-3, scene_q=None):
     """Many ``plan_trajectory`` problems in one launch (kin_traj_opt_batch): Q_start / Q_goal [n_dof, n_traj]
     (or one [n_dof] vector for every trajectory) -> (X [n_dof, n_traj * n_wp], iters [n_traj], info [4, n_traj]).
     Trajectory t is X[:, t * n_wp:(t + 1) * n_wp]; it is feasible (every interior sphere distance >= margin -
@@ -325,9 +374,21 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     dtype)).  Unless X0 is given, the constrained waypoint is solved first by the batched IK (kin_ik_dls_batch, 64
     iterations to 1e-6, from that waypoint of the straight line) and the guess is two straight lines, start -> IK
     answer -> goal.  info then has 6 rows (4: |r_p|, 5: |r_rot|), and a trajectory with iters[t] <= max_iters also
-    meets the constraint to `pose_tol`."""
+    meets the constraint to `pose_tol`.
+
+    With an ``AttachedUnionSDF`` as `sdf` (kin_traj_opt_scene_batch): `scene_q` holds its scene columns as a tensor
+    of `dtype` on the device, (n_scene_cols,) for every waypoint of every trajectory, (n_scene_cols, n_traj) per
+    trajectory or (n_scene_cols, n_traj * n_wp) per waypoint (``traj_opt_scene_batch``); `check_ends` evaluates
+    the starts at the scene state of waypoint 0 and the goals at that of waypoint n_wp - 1.  `pose_link` together
+    with an attached union raises."""
     n_wp = int(n_wp)
     dev = _device()
+    attached = isinstance(sdf, AttachedUnionSDF)
+    if attached and pose_link is not None:
+        raise ValueError("pose_link with an AttachedUnionSDF: pose constraints against a moving scene are not "
+                         "supported (kin_traj_opt_scene_batch takes none)")
+    if attached != (scene_q is not None):
+        raise ValueError("scene_q goes with an AttachedUnionSDF (and an AttachedUnionSDF needs it)")
     if pose_link is None:
         if pose_wp is not None or pose_targets is not None:
             raise ValueError("pose_wp / pose_targets need pose_link")
@@ -363,7 +424,24 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     n_traj = Qs.shape[1]
     st = stream or torch.cuda.current_stream(dev)
     with torch.cuda.stream(st):
-        if check_ends:
+        if attached:
+            if not isinstance(scene_q, torch.Tensor) or scene_q.dtype != dtype:
+                raise ValueError(f"scene_q must be a {dtype} tensor")
+            nc = sdf.n_scene_cols
+            if scene_q.dim() == 2 and scene_q.shape == (nc, n_traj * n_wp):
+                ends = scene_q.reshape(nc, n_traj, n_wp)
+                sq_ends = torch.cat([ends[:, :, 0], ends[:, :, n_wp - 1]], 1).contiguous()
+            elif scene_q.dim() == 2 and scene_q.shape == (nc, n_traj):
+                sq_ends = torch.cat([scene_q, scene_q], 1).contiguous()
+            elif scene_q.dim() == 1 and scene_q.shape[0] == nc:
+                sq_ends = scene_q.contiguous()
+            else:
+                raise ValueError(f"scene_q must be ({nc},), ({nc}, {n_traj}) or ({nc}, {n_traj * n_wp})")
+        if check_ends and attached:
+            _, _, mn = plan.run(sdf, torch.cat([Qs, Qg], 1), dists=False, min_dist=True, stream=st, scene_q=sq_ends)
+            if not bool((mn > 0).all()):
+                raise AssertionError("start / goal in collision")
+        elif check_ends:
             _, _, mn = plan.run(sdf, torch.cat([Qs, Qg], 1), dists=False, min_dist=True, stream=st)
             if not bool((mn > 0).all()):
                 raise AssertionError("start / goal in collision")
@@ -397,7 +475,11 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
             X[:, :, c] = Qm
             X[:, :, n_wp - 1] = Qg
             X = X.reshape(n_dof, n_traj * n_wp).contiguous()
-        if pose_link is None:
+        if attached:
+            it, nf = traj_opt_scene_batch(plan, sdf, X, n_wp, scene_q, margin=margin, band=band, weight=weight, feas=feas,
+                                          ftol=ftol, max_step=max_step, max_iters=max_iters, dof_weights=dof_weights,
+                                          stream=st)
+        elif pose_link is None:
             opt = traj_opt_tree_batch if plan.n_parts > 1 else traj_opt_batch
             it, nf = opt(plan, sdf, X, n_wp, margin=margin, band=band, weight=weight, feas=feas, ftol=ftol,
                          max_step=max_step, max_iters=max_iters, dof_weights=dof_weights, stream=st)
@@ -410,7 +492,7 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
 
 
 def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_start, q_goal, n_wp: int,
-                    margin=2e-2, partial_consts=(), ftol_abs=1e-3, solver="SLSQP_BOUNDED", maxiter=200):
+                    margin=2e-2, partial_consts=(), ftol_abs=1e-3, solver="SLSQP_BOUNDED", maxiter=200, scene_q=None):
     """src/planning.jl:332-401 -> (q_seq [n_dof, n_wp], status).  Constraint evaluations on the GPU.
 
     ``solver``: "SLSQP_BOUNDED" (SciPy SLSQP + joint-limit bounds; status ``:SUCCESS`` /
@@ -419,7 +501,9 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
     penalty descent of ``plan_trajectories`` on a batch of one (fp64; `partial_consts` empty or exactly one
     ``PoseConstraint`` with one move link at an interior waypoint, held by the kernel's constrained update with
     the axis-angle residual to 1e-3; status ``:SUCCESS`` when it ended feasible within `maxiter`, else
-    ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used)."""
+    ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used).  "GPU" only: `sdf` may be an ``AttachedUnionSDF`` with
+    `scene_q` its scene columns, (n_scene_cols,) or (n_scene_cols, n_wp) -- one scene state per waypoint
+    (kin_traj_opt_scene_batch; no partial constraint then)."""
     from scipy.optimize import minimize
     from .collision import compute_coll_dists
 
@@ -435,6 +519,8 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
                 raise ValueError(f"solver 'GPU': the PoseConstraint's idx_wp must be interior (2..{int(n_wp) - 1})")
             kw = dict(pose_link=pc.move_links[0], pose_wp=pc.idx_wp - 1, pose_targets=pc.target_poses[0],
                       pose_with_rot=pc.with_rots[0])
+        if scene_q is not None:
+            kw["scene_q"] = torch.as_tensor(scene_q, dtype=torch.float64).to(_device())
         X, it, _ = plan_trajectories(sscc, joints, sdf, np.asarray(q_start, np.float64), np.asarray(q_goal, np.float64),
                                      n_wp, margin=margin, max_iters=maxiter, dtype=torch.float64, **kw)
         return X.cpu().numpy(), (":SUCCESS" if int(it[0]) <= maxiter else ":MAXEVAL_REACHED")
@@ -443,6 +529,8 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
                          "(SciPy SLSQP with the joint-limit bounds) or 'SCIPY'")
     if solver not in ("SLSQP_BOUNDED", "SCIPY"):
         raise ValueError(f"unknown solver {solver!r}")
+    if scene_q is not None or isinstance(sdf, AttachedUnionSDF):
+        raise ValueError("an AttachedUnionSDF / scene_q needs solver='GPU'")
     m = sscc.mech
     n_dof = len(joints) + (3 if m.with_base else 0)
     assert len(q_start) == n_dof and len(q_goal) == n_dof

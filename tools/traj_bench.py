@@ -7,6 +7,7 @@ the host, one GPU constraint evaluation per iterate) looped over the same 32 pro
 
     python tools/traj_bench.py [--reps 5] [--no-slsqp] [--out profiles/traj_bench.json]
     python tools/traj_bench.py --scene pr2 [--out profiles/traj_bench_pr2.json]
+    python tools/traj_bench.py --scene pr2-door [--out profiles/traj_bench_scene.json]
 
 --scene pr2: the reference's fridge_demo.jl shape -- the PR2 (tests/golden/pr2_two_arms.urdf) with both arms and
 the planar base (17 columns), kinhip.PR2_ARM_SPHERES on two chains (kin_traj_opt_tree_batch), the static fridge
@@ -14,6 +15,14 @@ union at door 2.0 and base (1.2, 0, 0), from PR2_MANIP_POSE to 32 collision-free
 offsets of up to +-0.6 rad, the base driven 0.2-0.7 towards the fridge, +-0.15 sideways and turned by up to +-0.3,
 from default_rng(0); the first 32 with every sphere more than 0.05 clear).  straight_infeasible_of_32 counts the
 problems whose straight line does not clear the fridge by margin - feas.
+
+--scene pr2-door: the pr2 leg's robot, goals and fridge through kin_traj_opt_scene_batch (k_traj_scene), the fridge an
+AttachedUnionSDF(fridge, [door_joint]): (a) "uniform", one scene state for the launch (lds = 0) at door 2.0 and base
+(1.2, 0, 0) -- the same problems as the pr2 leg -- and (b) "swing", a scene state per waypoint, the door closing from
+2.0 to 1.2 over the waypoints of every trajectory; beside them, in the same process and with the repeats
+interleaved (static, uniform, swing, static, ...), "static": kin_traj_opt_tree_batch on the static snapshot, and
+ratio_to_static = the uniform leg's median over that one's.  Feasibility is re-evaluated with kin_coll_batch_scene
+at every waypoint's own scene state.
 
 Timing: a host clock around calls that end in a device synchronise, after a warm-up call per shape; the median of
 --reps repeats and their min / max.  Iterations per second counts, per trajectory, the iterations the kernel ran
@@ -91,9 +100,61 @@ def goals(m, joints, sscc, sdf, n=32):
     return Q[:, ok].contiguous()
 
 
-def interior_clearance(cp64, sdf, X, n_traj):
-    _, _, mn = cp64.run(sdf, X.double(), dists=False, min_dist=True)
+def interior_clearance(cp64, sdf, X, n_traj, scene_q=None):
+    _, _, mn = cp64.run(sdf, X.double(), dists=False, min_dist=True, scene_q=scene_q)
     return mn.reshape(n_traj, N_WP)[:, 1:-1].min(1).values
+
+
+def timed_interleaved(fns, reps):
+    """timed() for several calls with their repeats interleaved (a, b, c, a, b, c, ...): one warm-up each."""
+    for fn in fns:
+        fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(reps):
+        for k, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts[k].append(time.perf_counter() - t0)
+    return [(float(np.median(t)), float(min(t)), float(max(t))) for t in ts]
+
+
+def door_legs(a, res, joints, sscc, sdf, q_start, G, cp64):
+    """--scene pr2-door: static (k_traj_tree) / uniform (k_traj_scene, lds = 0) / swing (a scene state per waypoint)."""
+    fridge = kinhip.parse_urdf(os.path.join(ROOT, "tests", "golden", "fridge.urdf"), with_base=True)
+    att = kinhip.AttachedUnionSDF(fridge, [fridge.find_joint("door_joint")])
+    state = [2.0, 1.2, 0.0, 0.0]                                 # door, base x, y, theta: fridge_sdf's snapshot
+    for dtype in (torch.float32, torch.float64):
+        cp = sscc.plan(joints, dtype=dtype)
+        for n_traj in (32, 1024, 32768):
+            Qg = G.repeat(1, n_traj // 32).to(dtype).contiguous()
+            uni = torch.tensor(state, dtype=dtype, device="cuda")
+            swing = uni[:, None].repeat(1, n_traj * N_WP)
+            swing[0] = torch.linspace(2.0, 1.2, N_WP, dtype=dtype, device="cuda").repeat(n_traj)
+            legs = (("static", sdf, None), ("uniform", att, uni), ("swing", att, swing))
+            out = {}
+
+            def call_of(mode, s, sq):
+                def call():
+                    out[mode] = kinhip.plan_trajectories(sscc, joints, s, q_start, Qg, N_WP, margin=MARGIN, feas=FEAS,
+                                                         max_iters=MAX_ITERS, dtype=dtype, plan=cp, check_ends=False,
+                                                         scene_q=sq)
+                return call
+            times = timed_interleaved([call_of(*leg) for leg in legs], a.reps)
+            for (mode, s, sq), (med, lo, hi) in zip(legs, times):
+                X, it, info = out[mode]
+                ran = torch.clamp(it, max=MAX_ITERS).sum().item()
+                d = interior_clearance(cp64, s, X, n_traj, None if sq is None else sq.double())
+                feas32 = int((d[:32] >= MARGIN - FEAS - (1e-6 if dtype == torch.float32 else 0.0)).sum())
+                row = {"mode": mode, "dtype": str(dtype).split(".")[-1], "n_traj": n_traj, "seconds_median": med,
+                       "seconds_min": lo, "seconds_max": hi, "traj_per_s": n_traj / med, "iters_per_s": ran / med,
+                       "mean_iters": ran / n_traj, "feasible_of_32": feas32,
+                       "done_of_32": int((it[:32] <= MAX_ITERS).sum())}
+                if mode == "uniform":
+                    row["ratio_to_static"] = med / times[0][0]
+                res["gpu"].append(row)
+                print(json.dumps(row), flush=True)
 
 
 def timed(fn, reps):
@@ -113,11 +174,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no-slsqp", action="store_true")
     ap.add_argument("--out", default="")
-    ap.add_argument("--scene", choices=("fetch", "pr2"), default="fetch")
+    ap.add_argument("--scene", choices=("fetch", "pr2", "pr2-door"), default="fetch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("traj_bench.py needs a GPU")
-    if a.scene == "pr2":
+    if a.scene in ("pr2", "pr2-door"):
         m, joints, sscc, sdf = scene_pr2()
         ra, la, _ = kinhip.PR2_MANIP_POSE
         q_start = np.concatenate([np.deg2rad(np.array(ra + la)), np.zeros(3)])
@@ -135,6 +196,12 @@ def main():
     res = {"scene": name, "n_wp": N_WP, "max_iters": MAX_ITERS, "parts": cp64.n_parts,
            "straight_infeasible_of_32": int((d0 < MARGIN - FEAS).sum()), "gpu": []}
     print(json.dumps({k: v for k, v in res.items() if k != "gpu"}), flush=True)
+    if a.scene == "pr2-door":
+        door_legs(a, res, joints, sscc, sdf, q_start, G, cp64)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        return
     for dtype in (torch.float32, torch.float64):
         cp = sscc.plan(joints, dtype=dtype)
         for n_traj in (32, 1024, 32768):
