@@ -2,6 +2,7 @@
 // inverse_kinematics!, src/inverse_kinematics.jl:1-21): the generic kernels and the launcher of the
 // generic and plan-specialised forms.  (gfx950 only; the body is kinhip_ikt_dev.h.)
 #include "kinhip_ikt_dev.h"
+#include "kinhip_ik_launch.h"
 
 namespace kinhip {
 namespace {
@@ -23,26 +24,15 @@ __global__ __launch_bounds__(64) void k_ik_tree(const KIkcProg<T> P, const KIkcS
 
 }  // namespace
 
-// Lanes of a k_ik_tree target (specialised kernels): G attempt groups run a target's restart attempts
-// side by side, S sphere lanes per group share out its spheres -- identical results for every (S, G).
-// Small batches fill the chip only this way (the bistage solve's few thousand targets are a fraction of
-// a wave per SIMD): G = 4 while there are restart attempts and up to 2^16 targets, S = 16 while the
-// whole batch stays within ~4 waves per SIMD (n * G * 16 <= 2^18 lanes), else S = 1.
-// kin_ik_params.lanes forces a form: 1 = one lane, 2 / 4 / 8 = 4 attempt groups of one lane, 16 = 16
-// sphere lanes x 1, 64 = 16 x 4; KINHIP_IKT_S / KINHIP_IKT_G override (A/B build).
-static int ikt_variant(int64_t n, int natt, int lanes) {
-    static const int s_env = ab_env_int("KINHIP_IKT_S", 0), g_env = ab_env_int("KINHIP_IKT_G", 0);
-    if (lanes == 1) return 0;
-    if (lanes == 2 || lanes == 4 || lanes == 8) return 1;
-    if (lanes == 16) return 2;
-    if (lanes == 64) return 3;
-    int G = natt >= 2 && n <= (int64_t(1) << 16) ? 4 : 1;
-    int S = n * G * 16 <= (int64_t(1) << 18) ? 16 : 1;
-    if (s_env) S = s_env;
-    if (g_env) G = g_env;
-    for (int v = 0; v < kIktVariants; ++v)
-        if (kIktS[v] == S && kIktG[v] == G) return v;
-    return 0;
+// The lanes of a target are decided in kinhip_ik_sched.h (ikt_variant, ikt_generic_groups); its knobs (A/B build).
+static const IkKnobs& ikt_knobs() {
+    static const IkKnobs knobs = [] {
+        IkKnobs k;
+        k.ikt_s = ab_env_int("KINHIP_IKT_S", k.ikt_s);
+        k.ikt_g = ab_env_int("KINHIP_IKT_G", k.ikt_g);
+        return k;
+    }();
+    return knobs;
 }
 
 template <typename T>
@@ -50,19 +40,16 @@ hipError_t launch_ik_tree(const KIkcProg<T>& P, const KIkcStep<T>* steps, const 
                           const CollArgs& ca, const SceneLaunch* scene, const IkcArgs& c, const IkArgs& a,
                           const T* target, int64_t ldt, const T* q0, T* q, int64_t ldq, int64_t n, int32_t* iters,
                           T* err, int64_t lde, const JitFns* jf, hipStream_t st) {
-    int L, natt;
-    ik_attempts(a, &L, &natt);
-    IkArgsT<T> at{a.max_iters, T(a.lambda * a.lambda), T(a.tol_pos), T(a.tol_rot), T(a.max_step), L, natt, a.seed,
-                  0, 0, 0, nullptr, nullptr, nullptr, 0u, nullptr, a.with_rot == 2 ? 1 : 0};
+    IkArgsT<T> at = ik_args<T>(a);
+    const int natt = at.n_attempts;
     const IkcArgsT<T> cz{T(c.margin), T(c.band), T(c.weight), T(c.feas)};
     const size_t lds = ca.n_boxes <= kCollLdsBoxes ? (size_t)ca.n_boxes * sizeof(KBox<T>) : 0;
     const int rows6 = a.with_rot ? 1 : 0;
     // specialised kernels: the static union (ikt), a union attached to a scene of at most 2 moving groups
     // (ikts, KIN_SPEC_IK_COLL_SCENE); a scene of more groups runs the generic kernel
-    const int vi = jf ? ikt_variant(n, natt, a.lanes) : 0;
+    const int vi = jf ? ikt_variant(ikt_knobs(), n, natt, a.lanes) : 0;
     const hipFunction_t jk = !jf ? nullptr : !scene ? jf->ikt[rows6][vi] : scene->ng <= 2 ? jf->ikts[rows6][vi] : nullptr;
-    // generic kernel: attempt groups side by side only when the caller asks for them (lanes 2 / 4 / 8)
-    const int gg = (a.lanes == 2 || a.lanes == 4 || a.lanes == 8) && natt > 1 && P.nv <= 12 ? 4 : 1;
+    const int gg = ikt_generic_groups(a.lanes, natt, P.nv);
     const int lanes = jk ? kIktS[vi] * kIktG[vi] : gg;
     SceneArgs<T> sa{};
     if (scene) {

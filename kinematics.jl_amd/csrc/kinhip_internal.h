@@ -4,6 +4,7 @@
 
 #include <cstdlib>
 
+#include "kinhip_ik_sched.h"
 #include "kinhip_prog.h"
 
 namespace kinhip {
@@ -63,10 +64,7 @@ struct JitFns {
     hipFunction_t ikt[2][4] = {};
     hipFunction_t ikts[2][4] = {};  // the same over a union attached to a scene of at most 2 moving groups
 };
-// sphere lanes S and attempt groups G of the specialised k_ik_tree kernels, by JitFns::ikt index
-constexpr int kIktVariants = 4;
-constexpr int kIktS[kIktVariants] = {1, 1, 16, 16};
-constexpr int kIktG[kIktVariants] = {1, 4, 1, 4};
+// (kIktVariants, kIktS, kIktG: kinhip_ik_sched.h)
 
 // jf: the plan-specialised kernels (kinhip_jit.cpp) or null for the generic one
 template <typename T>
