@@ -549,9 +549,11 @@ KINHIP_API int kin_traj_metric_inverse(int32_t n_wp, double* out);
  * kin_traj_plan_create: kin_coll_plan_create plus the frames of 1..2 pose links for kin_traj_opt_pose_batch.  The
  * plan is a collision plan: every kin_coll_* call, kin_ineq_const_batch and kin_traj_opt_batch accept it, with the
  * results of a kin_coll_plan_create plan of the same desc (same sphere table).  The staged chain reaches the
- * deepest of the spheres and the pose links; a pose link must lie on the sphere chain or its extension (fixed
- * joints and joints held at the model's angles below a chain frame included), a link on another branch is
- * KIN_E_UNSUPPORTED, as are more than 2 links and a chain of more than 8 steps after the extension. */
+ * deepest of the spheres and the pose links; a pose link must lie on a sphere chain or its extension (fixed
+ * joints and joints held at the model's angles below a chain frame included): with spheres on several chains it
+ * rides on the first part, in plan order, whose chain is above, at or below it (kin_plan_pose_link_part).  A link
+ * on another branch than every part is KIN_E_UNSUPPORTED, as are more than 2 links and a carrying chain of more
+ * than 8 steps after the extension. */
 KINHIP_API int kin_traj_plan_create(const kin_model* m, const kin_coll_desc* desc, int32_t n_pose_links,
                                     const int32_t* pose_link_ids, kin_plan** out);
 typedef struct kin_traj_pose_params {
@@ -588,8 +590,8 @@ KINHIP_API int kin_traj_opt_pose_batch(const kin_plan* traj_plan, const kin_sdf*
  * kin_traj_opt_batch itself (the same kernel, bit-equal results).
  * Limits (KIN_E_UNSUPPORTED): at most 4 parts; every part's chain at most 16 steps; at most 20 q columns (+ base)
  * whatever the chain bounds; a static kin_sdf; 3 <= n_wp <= 64.
- * Not covered: pose constraints on a multi-chain plan (kin_traj_opt_pose_batch keeps refusing such plans, as does
- * kin_traj_opt_batch).  Unions attached to a scene: kin_traj_opt_scene_batch (this call refuses them). */
+ * Pose constraints on a multi-chain plan: kin_traj_opt_pose_tree_batch (kin_traj_opt_pose_batch keeps refusing such
+ * plans, as does kin_traj_opt_batch).  Unions attached to a scene: kin_traj_opt_scene_batch (this call refuses them). */
 KINHIP_API int kin_traj_opt_tree_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
                                        void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
                                        void* stream);
@@ -605,8 +607,8 @@ KINHIP_API int kin_traj_opt_tree_batch(const kin_plan* coll_plan, const kin_sdf*
  * Takes single-chain and multi-part plans of kin_coll_plan_create.  A static kin_sdf is KIN_E_INVALID (use
  * kin_traj_opt_tree_batch).  Limits (KIN_E_UNSUPPORTED): kin_traj_opt_tree_batch's (at most 4 parts, 16 steps per
  * part, 20 q columns (+ base), 3 <= n_wp <= 64) and a union of at most 2 moving groups (the fridge: its base and its
- * door).  Not covered: pose constraints with a scene; kin_plan_specialize_scene leaves this call on its generic
- * kernel.  Capture and the metric table as kin_traj_opt_batch (the same table).  Pinned against
+ * door).  Pose constraints with a scene: kin_traj_opt_pose_tree_batch.  kin_plan_specialize_scene leaves this call on
+ * its generic kernel.  Capture and the metric table as kin_traj_opt_batch (the same table).  Pinned against
  * tests/trajopt_scene_ref.py on tests/trajopt_scene_cases.py. */
 KINHIP_API int kin_traj_opt_scene_batch(const kin_plan* coll_plan, const kin_sdf* sdf, const kin_traj_params* prm,
                                         const void* scene_q, int64_t lds, void* xi, int64_t ldx, int64_t n_traj,
@@ -615,6 +617,25 @@ KINHIP_API int kin_traj_opt_scene_batch(const kin_plan* coll_plan, const kin_sdf
  * compiled chain bound (4 / 8 / 12 / 16 / 32) of part 0 .. count-1 (a single-chain plan: kin_plan_chain_bound) */
 KINHIP_API int kin_plan_part_count(const kin_plan* p, int32_t* out);
 KINHIP_API int kin_plan_part_chain_bound(const kin_plan* p, int32_t part, int32_t* out);
+/* the part (0 .. count-1) that carries pose link i of a kin_traj_plan_create plan; i out of range: KIN_E_KEY */
+KINHIP_API int kin_plan_pose_link_part(const kin_plan* p, int32_t i, int32_t* part);
+
+/* kin_traj_opt_pose_batch for every plan kind: pose link 0 of a kin_traj_plan_create plan held at a per-trajectory
+ * target at waypoint wp[0], with spheres on several chains (kin_traj_opt_tree_batch's sphere sum) and, with an
+ * attached kin_sdf, against a scene state per waypoint (kin_traj_opt_scene_batch's distances).  Residual, merit,
+ * constrained step, done rule, targets and the six info rows are kin_traj_opt_pose_batch's; the Jacobian is that of
+ * the part that carries the link, and the scene never enters the pose term (the target is a world pose).  One kernel,
+ * k_traj_pose_tree.  Pinned against tests/trajopt_pose_ref.py on tests/trajopt_pose_tree_cases.py.
+ *   static kin_sdf:   scene_q must be NULL and lds 0 (else KIN_E_INVALID); a single-chain plan runs
+ *                     kin_traj_opt_pose_batch itself (bit-equal results)
+ *   attached kin_sdf: scene_q / lds as kin_traj_opt_scene_batch; every plan through its part table
+ * Limits (KIN_E_UNSUPPORTED): a plan with pose links; every part's chain at most 8 steps; at most 4 parts; at most
+ * 20 q columns (+ base); at most 2 moving groups; n_con = 1; 3 <= n_wp <= 64.  Capture and the metric table as
+ * kin_traj_opt_batch (the same table). */
+KINHIP_API int kin_traj_opt_pose_tree_batch(const kin_plan* traj_plan, const kin_sdf* sdf, const kin_traj_params* prm,
+                                            const kin_traj_pose_params* pose, const void* targets, int64_t ldt,
+                                            const void* scene_q, int64_t lds, void* xi, int64_t ldx, int64_t n_traj,
+                                            int32_t* iters, void* info, int64_t ldi, void* stream);
 
 #ifdef __cplusplus
 }

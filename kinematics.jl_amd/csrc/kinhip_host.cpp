@@ -104,6 +104,14 @@ int kin_plan_part_chain_bound(const kin_plan* p, int32_t part, int32_t* out) {
     return KIN_OK;
 }
 
+int kin_plan_pose_link_part(const kin_plan* p, int32_t i, int32_t* part) {
+    if (!p || !part) return set_error(KIN_E_INVALID, "kin_plan_pose_link_part: null plan / part");
+    if (i < 0 || i >= (int32_t)p->pose_links.size())
+        return set_error(KIN_E_KEY, "kin_plan_pose_link_part: pose link index out of range");
+    *part = p->pose_links[i].part;
+    return KIN_OK;
+}
+
 namespace {
 int plan_run(const kin_plan* p, const void* q, int64_t ldq, int64_t n, void* poses, int64_t ldp, void* jac,
              int64_t ldj, const TileArgs& ta, void* stream, const char* fn) {
@@ -319,22 +327,27 @@ int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose,
         if (pose_ids[k] < 1 || pose_ids[k] > L) return set_error(KIN_E_KEY, fn + ": pose link id out of range");
     std::vector<char> done(c->n_spheres, 0);
     std::vector<std::unique_ptr<kin_plan>> parts;
+    // pose link k rides on the first part, in this order, whose spine is above, at or below its anchor; (part, index
+    // among that part's pose links), part -1: none yet
+    std::vector<std::pair<int32_t, int32_t>> pose_at(n_pose, {-1, 0});
     int32_t left = c->n_spheres;
     while (left > 0) {
         int32_t spine = -1, best = -1;
         for (int32_t k = 0; k < c->n_spheres; ++k)
             if (!done[k] && depth[k] > best) { best = depth[k]; spine = anchor[k]; }
-        const bool with_pose = n_pose > 0 && parts.empty();  // the pose links ride on the first (deepest) chain
-        for (int32_t k = 0; with_pose && k < n_pose; ++k) {  // ... or extend it: the chain reaches the deepest of them
+        std::vector<int32_t> pose_here;
+        for (int32_t k = 0; k < n_pose; ++k) {  // the links on this chain or its extension: it reaches the deepest of them
+            if (pose_at[k].first >= 0) continue;
             const int32_t a = anchor_of(pose_ids[k] - 1);
             bool above = false, below = false;  // a above (or at) the spine / the spine above a
             for (int32_t y = spine; y >= 0 && !above; y = m->plink(y)) above = y == a;
             for (int32_t y = a; y >= 0 && !below; y = m->plink(y)) below = y == spine;
-            if (!above && !below)
-                return set_error(KIN_E_UNSUPPORTED, fn + ": pose link " + std::to_string(k) +
-                                                        " is on another branch than the sphere chain");
+            if (!above && !below) continue;  // (another branch than this chain: a later part's, or none's)
             if (!above) spine = a;
+            pose_at[k] = {(int32_t)parts.size(), (int32_t)pose_here.size()};
+            pose_here.push_back(pose_ids[k]);
         }
+        const bool with_pose = !pose_here.empty();
         std::vector<char> on_path(L, 0);
         for (int32_t y = spine; y >= 0; y = m->plink(y)) on_path[y] = 1;
         std::vector<int32_t> ids, outs;
@@ -351,13 +364,25 @@ int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose,
         kin_coll_desc sub{c->dtype, c->n_q, c->q_joint_ids, (int32_t)ids.size(), ids.data(), cen.data(), rad.data()};
         kin_plan_desc d{c->dtype, c->n_q, c->q_joint_ids, 0, nullptr, spine + 1, c->n_q, c->q_joint_ids, 0};
         auto P = std::make_unique<kin_plan>();
-        if (const int rc = stage_plan(*m, d, &sub, outs.data(), *P, with_pose ? n_pose : 0, pose_ids)) return rc;
+        if (const int rc = stage_plan(*m, d, &sub, outs.data(), *P, (int32_t)pose_here.size(), pose_here.data())) return rc;
         if (with_pose && P->geom.maxA > kTrajPoseMaxChain)
             return set_error(KIN_E_UNSUPPORTED, fn + ": the chain to the deepest sphere / pose link has more than " +
                                                     std::to_string(kTrajPoseMaxChain) + " steps");
-        if (const int rc = upload_plan(*P)) return rc;
         parts.push_back(std::move(P));
     }
+    for (int32_t k = 0; k < n_pose; ++k)
+        if (pose_at[k].first < 0)
+            return set_error(KIN_E_UNSUPPORTED, fn + ": pose link " + std::to_string(k) +
+                                                    " is on another branch than the sphere chain");
+    // the top plan's pose links in the caller's order, each with the part that carries it (staged above, part by part)
+    std::vector<kin_plan::PoseLink> pose_links;
+    for (int32_t k = 0; k < n_pose; ++k) {
+        kin_plan::PoseLink pl = parts[pose_at[k].first]->pose_links[pose_at[k].second];
+        pl.part = pose_at[k].first;
+        pose_links.push_back(pl);
+    }
+    for (auto& P : parts)  // (nothing was uploaded before the last refusal above)
+        if (const int rc = upload_plan(*P)) return rc;
     std::unique_ptr<kin_plan> top;
     if (parts.size() == 1) {
         top = std::move(parts[0]);
@@ -375,6 +400,7 @@ int coll_plan_create(const kin_model* m, const kin_coll_desc* c, int32_t n_pose,
         if (const int rc = upload_traj_parts(*top, fn)) return rc;
     }
     top->n_sph = c->n_spheres;
+    top->pose_links = std::move(pose_links);
     for (int32_t k = 0; k < c->n_q; ++k) {  // (kin_traj_opt_batch clamps to these)
         top->col_lo.push_back(m->jlo[c->q_joint_ids[k] - 1]);
         top->col_hi.push_back(m->jhi[c->q_joint_ids[k] - 1]);

@@ -174,7 +174,7 @@ struct TrajPose {
     int32_t step;     // chain step whose post-motion frame carries the link (-1: the root / base frame)
     int32_t wp;       // the constrained waypoint (0-based, interior)
     int32_t with_rot;  // 0: 3 rows, 1: 6 rows
-    int32_t pad;
+    int32_t part;     // k_traj_pose_tree: the part of the table that carries the link (k_traj_pose: unused)
 };
 // k_traj_tree (kin_traj_opt_tree_batch): the spheres of every part of a multi-chain collision plan.  The parts
 // reach the kernel as one device table, staged with the top plan (kin_coll_plan_create): per part the program
@@ -191,7 +191,8 @@ struct TrajPart {
     int64_t steps_off;  // KStep<T>[common bound] (identity steps past the part's own program)
     int64_t sph_off;    // KSphere<T>[P.n_sph]
 };
-// One launcher for the three kernels; the descriptor says which one and carries what only that one takes.
+// One launcher for the kernels; the descriptor says which one and carries what only that one takes (tp with parts:
+// k_traj_pose_tree, with or without scene).
 template <typename T>
 struct TrajLaunch {
     const KProg<T>* P;  // the chain (k_traj, k_traj_pose; unused by k_traj_tree)
@@ -208,7 +209,7 @@ struct TrajLaunch {
     // and scene_q [cols][ld], sample t * n_wp + w = waypoint w of trajectory t (uniform: one set for the launch)
     const SceneLaunch* scene = nullptr;
 };
-// one chunk of launch_traj's loop for k_traj_scene (kinhip_traj_scene.hip; called by launch_traj only)
+// one chunk of launch_traj's loop for k_traj_scene (kinhip_traj_scene.hip) and k_traj_pose_tree; called by launch_traj only
 template <typename T>
 struct TrajSceneChunk {
     dim3 grid, block;
@@ -231,6 +232,11 @@ struct TrajSceneChunk {
 };
 template <typename T>
 bool launch_traj_scene_chunk(int maxA, int L, const TrajSceneChunk<T>& k);
+// the same for k_traj_pose_tree (kinhip_traj_pose_tree.hip): tp with its part, the chunk's first target column;
+// k.scene null for a static union (k.sample0 is then unused)
+template <typename T>
+bool launch_traj_pose_tree_chunk(int maxA, int L, const TrajSceneChunk<T>& k, TrajPose<T> tp, const T* targets,
+                                 int64_t ldt);
 // minv: (A_sub[I,I])^-1 of n_wp waypoints on the device, row-major (symmetric, so also its transpose)
 template <typename T>
 hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollArgs& a, const TrajArgs& ta,

@@ -207,10 +207,12 @@ struct kin_plan {
     mutable std::map<int32_t, void*> traj_minv;
     // kin_traj_plan_create: the pose links of kin_traj_opt_pose_batch (fp64 on the host; a kernel argument, never
     // part of the sphere table): the chain step whose post-motion frame carries the link (-1: the root / base
-    // frame) and the static transform from that frame to the link
+    // frame) and the static transform from that frame to the link; part: the part whose chain that is (the top plan's
+    // table; 0 for a single-chain plan)
     struct PoseLink {
         int32_t step;
         M34 X;
+        int32_t part = 0;
     };
     std::vector<PoseLink> pose_links;
     // kin_traj_opt_tree_batch: the part table of a multi-chain plan on the device, [TrajPart<T>[n_parts] | every

@@ -74,13 +74,13 @@ bool traj_dispatch(int maxA, int L, F&& f) {
 
 }  // namespace
 
-// d.tp selects k_traj_pose, d.parts k_traj_tree (with d.scene: k_traj_scene), neither k_traj; each with the chain
-// bounds it is compiled for
+// d.tp selects k_traj_pose, d.parts k_traj_tree (with d.scene: k_traj_scene), both k_traj_pose_tree, neither k_traj;
+// each with the chain bounds it is compiled for
 template <typename T>
 hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollArgs& a, const TrajArgs& ta,
                        const TrajDof& dof, const T* minvT, T* xi, int64_t ldx, int64_t n_traj, int32_t* iters, T* info,
                        int64_t ldi, hipStream_t st) {
-    if (d.scene && (!d.parts || d.tp)) return hipErrorInvalidValue;
+    if (d.scene && !d.parts) return hipErrorInvalidValue;
     if (d.parts && (d.n_parts < 1 || d.n_parts > kTrajMaxParts || d.ndof > kTrajNdLarge)) return hipErrorInvalidValue;
     const int L = traj_segment(ta.n_wp);
     // the largest workgroup (whole waves) whose LDS stays within 64 KiB
@@ -103,11 +103,12 @@ hipError_t launch_traj(const TrajLaunch<T>& d, const KBox<T>* boxes, const CollA
                 hipLaunchKernelGGL((k_traj<T, decltype(m)::value, decltype(l)::value>), grid, blk, lds, st, *d.P, d.steps,
                                    d.sph, boxes, a, ta, dof, minvT, xc, ldx, c, ic, fc, ldi);
             });
-        else if (d.scene)
-            compiled = launch_traj_scene_chunk<T>(d.maxA, L, TrajSceneChunk<T>{grid, blk, lds, st, d.parts, d.n_parts, d.ndof,
-                                                                              boxes, &a, &ta, &dof, minvT, d.scene,
-                                                                              t0 * ta.n_wp, xc, ldx, c, ic, fc, ldi});
-        else if (d.tp)
+        else if (d.parts && (d.scene || d.tp)) {
+            const TrajSceneChunk<T> k{grid, blk, lds, st, d.parts, d.n_parts, d.ndof, boxes, &a, &ta, &dof, minvT, d.scene,
+                                      t0 * ta.n_wp, xc, ldx, c, ic, fc, ldi};
+            compiled = d.tp ? launch_traj_pose_tree_chunk<T>(d.maxA, L, k, *d.tp, tc, d.ldt)
+                            : launch_traj_scene_chunk<T>(d.maxA, L, k);
+        } else if (d.tp)
             compiled = traj_dispatch<4, 8>(d.maxA, L, [&](auto m, auto l) {
                 hipLaunchKernelGGL((k_traj_pose<T, decltype(m)::value, decltype(l)::value>), grid, blk, lds, st, *d.P,
                                    d.steps, d.sph, boxes, a, ta, dof, *d.tp, minvT, tc, d.ldt, xc, ldx, c, ic, fc, ldi);

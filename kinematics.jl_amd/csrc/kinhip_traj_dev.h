@@ -1,5 +1,6 @@
-// kinhip_traj_dev.h -- traj_body, the one device body of k_traj (kin_traj_opt_batch), k_traj_pose (POSE) and k_traj_tree
-// (TREE).  Included by kinhip_traj.hip only (no run-time specialisation: not part of the embedded sources).  gfx950 only.
+// kinhip_traj_dev.h -- traj_body, the one device body of k_traj (kin_traj_opt_batch), k_traj_pose (POSE), k_traj_tree
+// (TREE), k_traj_scene (SCENE) and k_traj_pose_tree (POSE and TREE, any SCENE).  Included by the kinhip_traj*.hip units
+// only (no run-time specialisation: not part of the embedded sources).  gfx950 only.
 //
 // Many independent trajectories of n_wp waypoints per launch, one lane per waypoint, each trajectory
 // in a wave segment of L = 8 / 16 / 32 / 64 lanes (the smallest L >= n_wp).  Per iteration a lane
@@ -17,6 +18,9 @@
 // TREE = true (kin_traj_opt_tree_batch, common bounds 8 and 16): the POSE = false loop with the sphere sum of the merit
 // and its half-gradient taken over every part of a multi-chain plan: a lane walks part after part in plan order, the
 // walk state of a part dead before the next one starts.  Always ND = kTrajNdLarge columns; ndof is a kernel argument.
+//
+// POSE and TREE (kin_traj_opt_pose_tree_batch, k_traj_pose_tree in kinhip_traj_pose_tree.hip): the pose link rides on
+// part tp.part of the table: that part's walk captures its frame, the Newton walk runs on that part's program.
 //
 // SCENE != 0 (kin_traj_opt_scene_batch, k_traj_scene in kinhip_traj_scene.hip; TREE only): the union's boxes are
 // attached to a scene mechanism of at most SCENE moving groups and every waypoint has its own scene state: the lane
@@ -372,7 +376,7 @@ __device__ __forceinline__ void traj_pose_newton(const KProg<T>& P, const KStep<
     for (int k = 0; k < ND; ++k) u[k] *= (T)dof.iW[k];
 }
 
-// P, S, sph: the chain (not TREE); tp, targets, ldt: POSE only; parts, n_parts, nd (q columns + base): TREE only;
+// P, S, sph: the chain (not TREE); tp, targets, ldt: POSE only (tp->part: TREE); parts, n_parts, nd (q columns + base): TREE only;
 // sa: SCENE != 0 only (its q already at the launch chunk's first sample)
 template <typename T, int MAXA, int L, bool POSE = false, bool TREE = false, int SCENE = 0>
 __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __restrict__ S,
@@ -384,7 +388,7 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                                           const T* __restrict__ targets = nullptr, int64_t ldt = 0,
                                           const TrajPart<T>* __restrict__ parts = nullptr, int n_parts = 0, int nd = 0,
                                           const SceneArgs<T>* sa = nullptr) {
-    static_assert(SCENE == 0 || (TREE && !POSE), "the scene variant is the part loop's");
+    static_assert(SCENE == 0 || TREE, "the scene variant is the part loop's");
     constexpr int ND = TREE ? kTrajNdLarge : TrajNd<MAXA>::v;
     const int n_wp = ta.n_wp, ni = n_wp - 2;
     const int ndof = TREE ? nd : P.n_jac + ((P.flags & PF_BASE) ? 3 : 0);
@@ -442,7 +446,7 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
         // ---- the merit and its half-gradient at xn ----
         T pen, dmin;
         T rpn = T(0), rrn = T(0);  // POSE: |r_p|, |r_rot| of the segment's candidate
-        if constexpr (POSE) {
+        if constexpr (POSE && !TREE) {
             Fr<T> Cf;
             set_identity(Cf);
             traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc,
@@ -459,13 +463,26 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
             dmin = T(INFINITY);
 #pragma unroll
             for (int k = 0; k < ND; ++k) gn[k] = T(0);
+            Fr<T> Cf;  // POSE: the frame that carries the pose link, from the walk of part tp->part
+            if constexpr (POSE) set_identity(Cf);
             for (int p = 0; p < n_parts; ++p) {  // (uniform; the chain inside stays unrolled)
                 const TrajPart<T>& pt = parts[p];
                 const char* tab = reinterpret_cast<const char*>(parts);  // (offsets from the kernel argument: global loads)
                 const KStep<T>* __restrict__ Sp = reinterpret_cast<const KStep<T>*>(tab + pt.steps_off);
                 const KSphere<T>* __restrict__ sp = reinterpret_cast<const KSphere<T>*>(tab + pt.sph_off);
                 T gp[ND], penp, dminp;
-                if constexpr (SCENE != 0)
+                if constexpr (POSE) {
+                    // one call site: the hook's step is -2 (no frame of the walk) on the parts without the pose link
+                    const TrajFrameAt<T> hook{p == tp->part ? tp->step : -2, Cf};  // (uniform)
+                    if constexpr (SCENE != 0)
+                        traj_penalty<T, MAXA, ND, TrajFrameAt<T>, SCENE>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes,
+                                                                         smem, use_lds, xn, interior, trunc, weight, gp,
+                                                                         penp, dminp, hook, &sc);
+                    else
+                        traj_penalty<T, MAXA, ND, TrajFrameAt<T>>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem,
+                                                                  use_lds, xn, interior, trunc, weight, gp, penp, dminp,
+                                                                  hook);
+                } else if constexpr (SCENE != 0)
                     traj_penalty<T, MAXA, ND, TrajNoHook, SCENE>(pt.P, Sp, sp, boxes, aabb, a.n_aabb, a.n_boxes, smem,
                                                                  use_lds, xn, interior, trunc, weight, gp, penp, dminp,
                                                                  TrajNoHook(), &sc);
@@ -476,6 +493,13 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                 for (int k = 0; k < ND; ++k) gn[k] += gp[k];
                 pen += penp;
                 dmin = fmin(dmin, dminp);
+            }
+            if constexpr (POSE) {  // once per iteration, after the part loop (the scene never enters the pose term)
+                T r[6], pl[3];
+                traj_pose_residual(Cf, *tp, tg, r, pl);
+                traj_pose_norms(r, rpn, rrn);
+                rpn = __shfl(rpn, tp->wp, L);
+                rrn = __shfl(rrn, tp->wp, L);
             }
         } else {
             traj_penalty<T, MAXA, ND>(P, S, sph, boxes, aabb, a.n_aabb, a.n_boxes, smem, use_lds, xn, interior, trunc,
@@ -555,7 +579,14 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
                 xc[k] = __shfl(x[k], tp->wp, L);
                 rawc[k] = __shfl(st[k], tp->wp, L);
             }
-            traj_pose_newton<T, MAXA, ND>(P, S, *tp, tg, dof, xc, rawc, u);
+            if constexpr (TREE) {  // the program of the part that carries the pose link (offsets from the kernel argument)
+                const TrajPart<T>& pt = parts[tp->part];
+                const KStep<T>* __restrict__ Sp =
+                    reinterpret_cast<const KStep<T>*>(reinterpret_cast<const char*>(parts) + pt.steps_off);
+                traj_pose_newton<T, MAXA, ND>(pt.P, Sp, *tp, tg, dof, xc, rawc, u);
+            } else {
+                traj_pose_newton<T, MAXA, ND>(P, S, *tp, tg, dof, xc, rawc, u);
+            }
             const int ci = tp->wp - 1;
             const T ratio = mt[ci * ni + wi] / mt[ci * ni + ci];
 #pragma unroll
@@ -593,6 +624,21 @@ __device__ __forceinline__ void traj_body(const KProg<T>& P, const KStep<T>* __r
             }
         }
     }
+}
+
+// host side of the SCENE != 0 kernels: the scene arguments of one chunk of launch_traj's loop, sample0 the chunk's
+// first sample (t0 * n_wp, as xi); uniform: the scene values are one column of cols entries
+template <typename T>
+SceneArgs<T> traj_scene_args(const SceneLaunch& s, int64_t sample0) {
+    SceneArgs<T> sa;
+    sa.groups = (const KSceneGroup*)s.groups;
+    sa.steps = (const KSceneStep<T>*)s.steps;
+    sa.q = (const T*)s.q + (s.uniform ? 0 : sample0);
+    sa.ld = s.uniform ? 1 : s.ld;
+    sa.ng = s.ng;
+    sa.base_col = s.base_col;
+    sa.uniform = s.uniform;
+    return sa;
 }
 
 }  // namespace

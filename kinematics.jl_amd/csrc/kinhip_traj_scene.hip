@@ -43,15 +43,7 @@ bool scene_at(int L, const TrajSceneChunk<T>& k, const SceneArgs<T>& sa) {
 template <typename T>
 bool launch_traj_scene_chunk(int maxA, int L, const TrajSceneChunk<T>& k) {
     if (k.scene->ng < 1 || k.scene->ng > kTrajSceneGroups) return false;
-    SceneArgs<T> sa;
-    sa.groups = (const KSceneGroup*)k.scene->groups;
-    sa.steps = (const KSceneStep<T>*)k.scene->steps;
-    // the chunk's first sample (t0 * n_wp, as xi); uniform: the scene values are one column of cols entries
-    sa.q = (const T*)k.scene->q + (k.scene->uniform ? 0 : k.sample0);
-    sa.ld = k.scene->uniform ? 1 : k.scene->ld;
-    sa.ng = k.scene->ng;
-    sa.base_col = k.scene->base_col;
-    sa.uniform = k.scene->uniform;
+    const SceneArgs<T> sa = traj_scene_args<T>(*k.scene, k.sample0);
     return maxA == 8 ? scene_at<T, 8>(L, k, sa) : maxA == 16 ? scene_at<T, 16>(L, k, sa) : false;
 }
 

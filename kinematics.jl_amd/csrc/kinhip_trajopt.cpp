@@ -1,7 +1,8 @@
 // kinhip_trajopt.cpp -- C-ABI of the batched trajectory optimiser: kin_traj_opt_batch (k_traj,
 // kinhip_traj.hip), kin_traj_opt_pose_batch (its POSE variant: one pose link held at a waypoint),
 // kin_traj_opt_tree_batch (k_traj_tree: spheres on several chains), kin_traj_opt_scene_batch (k_traj_scene: the
-// union attached to a scene, one scene state per waypoint) and their metric table.
+// union attached to a scene, one scene state per waypoint), kin_traj_opt_pose_tree_batch (k_traj_pose_tree: the pose
+// link on either of the two) and their metric table.
 //
 // Reference semantics restated here (host side):
 //   Objective's A_sub (finite-difference accelerations)    src/planning.jl:1-28
@@ -107,6 +108,24 @@ int traj_check_params(const Bad& bad, const kin_traj_params* prm) {
     return KIN_OK;
 }
 
+// the pose parameter block and the targets (after traj_check_params): need no plan and no device either
+int traj_check_pose(const Bad& bad, const kin_traj_params* prm, const kin_traj_pose_params* pose, const void* targets,
+                    int64_t ldt, int64_t n_traj) {
+    if (!pose) return bad(KIN_E_INVALID, "null pose parameters");
+    if (pose->n_con != 1) return bad(KIN_E_UNSUPPORTED, "n_con must be 1 (one pose constraint per trajectory)");
+    if (!pose->wp || !pose->with_rot) return bad(KIN_E_INVALID, "null wp / with_rot");
+    if (pose->wp[0] < 1 || pose->wp[0] > prm->n_wp - 2)
+        return bad(KIN_E_INVALID, "wp must be an interior waypoint, 1.." + std::to_string(prm->n_wp - 2));
+    if (pose->with_rot[0] != 0 && pose->with_rot[0] != 1) return bad(KIN_E_INVALID, "with_rot must be 0 or 1");
+    if (!(pose->weight > 0) || !std::isfinite(pose->weight))
+        return bad(KIN_E_INVALID, "pose weight must be finite and > 0");
+    if (!(pose->tol_pos > 0) || !std::isfinite(pose->tol_pos) || !(pose->tol_rot > 0) || !std::isfinite(pose->tol_rot))
+        return bad(KIN_E_INVALID, "tol_pos and tol_rot must be finite and > 0");
+    if (!(pose->damp >= 0) || !std::isfinite(pose->damp)) return bad(KIN_E_INVALID, "damp must be finite and >= 0");
+    if (n_traj > 0 && (!targets || ldt < n_traj)) return bad(KIN_E_INVALID, "bad targets / ldt (ldt >= n_traj)");
+    return KIN_OK;
+}
+
 // what follows the plan's own limits: joint limits, dof_weights, the arrays, the devices, the metric table
 // (*minv stays null for n_traj == 0: nothing to launch)
 int traj_check_arrays(const Bad& bad, const std::string& fn, const kin_plan* p, const kin_sdf* sdf,
@@ -188,6 +207,7 @@ int traj_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin
             tp.step = pl.step;
             tp.wp = pose->wp[0];
             tp.with_rot = pose->with_rot[0];
+            tp.part = pl.part;
         }
         // the chain, its bound and ndof (tree: the common bound, the plan's q columns), the pose arguments, the part table
         TrajLaunch<T> d{&P, p->steps<T>(), p->sph<T>(), tree ? p->traj_tree_maxA : p->geom.maxA,
@@ -198,7 +218,9 @@ int traj_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin
                               (const T*)minv, (T*)xi, ldx, n_traj, iters, (T*)info, ldi, (hipStream_t)stream);
     });
     if (e != hipSuccess)
-        return set_error(KIN_E_DEVICE, std::string(scene ? "k_traj_scene launch: " : tree ? "k_traj_tree launch: " : "k_traj launch: ") +
+        return set_error(KIN_E_DEVICE, std::string(tree && pose ? "k_traj_pose_tree launch: " : scene ? "k_traj_scene launch: "
+                                                   : tree       ? "k_traj_tree launch: "
+                                                                : "k_traj launch: ") +
                                            hipGetErrorString(e));
     return KIN_OK;
 }
@@ -210,20 +232,8 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
     const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
     // the parameters first (they need no plan), then the plan and the union, then the arrays
     if (const int rc = traj_check_params(bad, prm)) return rc;
-    if (with_pose) {
-        if (!pose) return bad(KIN_E_INVALID, "null pose parameters");
-        if (pose->n_con != 1) return bad(KIN_E_UNSUPPORTED, "n_con must be 1 (one pose constraint per trajectory)");
-        if (!pose->wp || !pose->with_rot) return bad(KIN_E_INVALID, "null wp / with_rot");
-        if (pose->wp[0] < 1 || pose->wp[0] > prm->n_wp - 2)
-            return bad(KIN_E_INVALID, "wp must be an interior waypoint, 1.." + std::to_string(prm->n_wp - 2));
-        if (pose->with_rot[0] != 0 && pose->with_rot[0] != 1) return bad(KIN_E_INVALID, "with_rot must be 0 or 1");
-        if (!(pose->weight > 0) || !std::isfinite(pose->weight))
-            return bad(KIN_E_INVALID, "pose weight must be finite and > 0");
-        if (!(pose->tol_pos > 0) || !std::isfinite(pose->tol_pos) || !(pose->tol_rot > 0) || !std::isfinite(pose->tol_rot))
-            return bad(KIN_E_INVALID, "tol_pos and tol_rot must be finite and > 0");
-        if (!(pose->damp >= 0) || !std::isfinite(pose->damp)) return bad(KIN_E_INVALID, "damp must be finite and >= 0");
-        if (n_traj > 0 && (!targets || ldt < n_traj)) return bad(KIN_E_INVALID, "bad targets / ldt (ldt >= n_traj)");
-    }
+    if (with_pose)
+        if (const int rc = traj_check_pose(bad, prm, pose, targets, ldt, n_traj)) return rc;
     if (const int rc = traj_check_plan(bad, p, sdf, true)) return rc;
     if (p->geom.maxA > kTrajMaxChain)
         return bad(KIN_E_UNSUPPORTED, "the sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
@@ -236,6 +246,35 @@ int traj_opt(const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const
         return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(nd_max) + " q columns (+ base) for this chain");
     return traj_run(bad, fn, p, sdf, prm, with_pose ? pose : nullptr, targets, ldt, xi, ldx, n_traj, iters, info, ldi,
                     stream);
+}
+
+// the part-table entry points' tail (k_traj_tree, k_traj_scene, k_traj_pose_tree): the limits of the part loop with
+// max_chain steps per part, the scene arrays of an attached union, then traj_run
+int traj_parts_run(const Bad& bad, const std::string& fn, const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+                   int max_chain, const kin_traj_pose_params* pose, const void* targets, int64_t ldt, const void* scene_q,
+                   int64_t lds, void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info, int64_t ldi,
+                   void* stream) {
+    if (sdf->attached && sdf->n_groups > kTrajSceneGroups)
+        return bad(KIN_E_UNSUPPORTED, "the union has " + std::to_string(sdf->n_groups) + " moving groups (at most " +
+                                          std::to_string(kTrajSceneGroups) + " moving groups)");
+    if ((int)p->parts.size() > kTrajMaxParts)
+        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
+                                          " chains (parts)");
+    bool ok = p->parts.empty() ? p->geom.maxA <= max_chain : true;
+    for (const auto& s : p->parts) ok = ok && s->geom.maxA <= max_chain;
+    if (!ok) return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(max_chain) + " steps");
+    if (p->nqcols > kTrajNdLarge)
+        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
+    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
+    if (!sdf->attached)
+        return traj_run(bad, fn, p, sdf, prm, pose, targets, ldt, xi, ldx, n_traj, iters, info, ldi, stream);
+    if (n_traj > 0 && n_traj <= (int64_t(1) << 40) / prm->n_wp && sdf->scene_cols > 0 &&
+        (!scene_q || (lds != 0 && lds < n_traj * prm->n_wp)))
+        return bad(KIN_E_INVALID, "bad scene_q / lds (lds = 0: one scene state, else lds >= n_traj * n_wp)");
+    const void* sc = p->dtype == KIN_F32 ? sdf->d_scene_f32 : sdf->d_scene_f64;
+    const SceneLaunch sl{sc, (const char*)sc + sdf->scene_steps_off, scene_q, lds, sdf->n_groups, sdf->scene_base_col,
+                         lds == 0 ? 1 : 0};
+    return traj_run(bad, fn, p, sdf, prm, pose, targets, ldt, xi, ldx, n_traj, iters, info, ldi, stream, &sl);
 }
 
 }  // namespace
@@ -262,16 +301,8 @@ int kin_traj_opt_tree_batch(const kin_plan* p, const kin_sdf* sdf, const kin_tra
     if (const int rc = traj_check_plan(bad, p, sdf, false)) return rc;
     if (p->parts.empty())  // (its remaining checks; the ones above pass again)
         return traj_opt(fn, p, sdf, prm, nullptr, false, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
-    if ((int)p->parts.size() > kTrajMaxParts)
-        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
-                                          " chains (parts)");
-    for (const auto& s : p->parts)
-        if (s->geom.maxA > kTrajMaxChain)
-            return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
-    if (p->nqcols > kTrajNdLarge)
-        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
-    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
-    return traj_run(bad, fn, p, sdf, prm, nullptr, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream);
+    return traj_parts_run(bad, fn, p, sdf, prm, kTrajMaxChain, nullptr, nullptr, 0, nullptr, 0, xi, ldx, n_traj, iters, info,
+                          ldi, stream);
 }
 
 // k_traj_scene: every plan through the part loop (a single-chain plan's one-entry table), the union attached to a scene
@@ -286,26 +317,30 @@ int kin_traj_opt_scene_batch(const kin_plan* p, const kin_sdf* sdf, const kin_tr
     if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
     if (!sdf->attached)
         return bad(KIN_E_INVALID, "the kin_sdf is not attached to a scene (a static union: kin_traj_opt_tree_batch)");
-    if (sdf->n_groups > kTrajSceneGroups)
-        return bad(KIN_E_UNSUPPORTED, "the union has " + std::to_string(sdf->n_groups) + " moving groups (at most " +
-                                          std::to_string(kTrajSceneGroups) + " moving groups)");
-    if ((int)p->parts.size() > kTrajMaxParts)
-        return bad(KIN_E_UNSUPPORTED, "the plan's spheres hang off more than " + std::to_string(kTrajMaxParts) +
-                                          " chains (parts)");
-    const auto chain_ok = [](const kin_plan& s) { return s.geom.maxA <= kTrajMaxChain; };
-    bool ok = p->parts.empty() ? chain_ok(*p) : true;
-    for (const auto& s : p->parts) ok = ok && chain_ok(*s);
-    if (!ok) return bad(KIN_E_UNSUPPORTED, "a sphere chain has more than " + std::to_string(kTrajMaxChain) + " steps");
-    if (p->nqcols > kTrajNdLarge)
-        return bad(KIN_E_UNSUPPORTED, "more than " + std::to_string(kTrajNdLarge) + " q columns (+ base)");
-    if (!p->d_traj_parts) return bad(KIN_E_INVALID, "plan without a part table");
-    if (n_traj > 0 && n_traj <= (int64_t(1) << 40) / prm->n_wp && sdf->scene_cols > 0 &&
-        (!scene_q || (lds != 0 && lds < n_traj * prm->n_wp)))
-        return bad(KIN_E_INVALID, "bad scene_q / lds (lds = 0: one scene state, else lds >= n_traj * n_wp)");
-    const void* sc = p->dtype == KIN_F32 ? sdf->d_scene_f32 : sdf->d_scene_f64;
-    const SceneLaunch sl{sc, (const char*)sc + sdf->scene_steps_off, scene_q, lds, sdf->n_groups, sdf->scene_base_col,
-                         lds == 0 ? 1 : 0};
-    return traj_run(bad, fn, p, sdf, prm, nullptr, nullptr, 0, xi, ldx, n_traj, iters, info, ldi, stream, &sl);
+    return traj_parts_run(bad, fn, p, sdf, prm, kTrajMaxChain, nullptr, nullptr, 0, scene_q, lds, xi, ldx, n_traj, iters,
+                          info, ldi, stream);
+}
+
+// k_traj_pose_tree: the pose link on a multi-part plan (static union) or on any plan against an attached union; a
+// single-chain plan against a static union runs kin_traj_opt_pose_batch's own path (the same k_traj_pose instantiation)
+int kin_traj_opt_pose_tree_batch(const kin_plan* p, const kin_sdf* sdf, const kin_traj_params* prm,
+                                 const kin_traj_pose_params* pose, const void* targets, int64_t ldt, const void* scene_q,
+                                 int64_t lds, void* xi, int64_t ldx, int64_t n_traj, int32_t* iters, void* info,
+                                 int64_t ldi, void* stream) {
+    const std::string fn = "kin_traj_opt_pose_tree_batch";
+    const Bad bad = [&](int code, const std::string& w) { return set_error(code, fn + ": " + w); };
+    if (const int rc = traj_check_params(bad, prm)) return rc;
+    if (const int rc = traj_check_pose(bad, prm, pose, targets, ldt, n_traj)) return rc;
+    if (lds < 0) return bad(KIN_E_INVALID, "lds < 0");
+    if (!p || !sdf) return bad(KIN_E_INVALID, "null plan / sdf");
+    if (!p->is_coll || p->is_coll_ik) return bad(KIN_E_INVALID, "plan was not made by kin_coll_plan_create");
+    if (!sdf->attached && (scene_q || lds != 0))
+        return bad(KIN_E_INVALID, "scene_q / lds with a static kin_sdf (scene_q must be NULL and lds 0)");
+    if (!sdf->attached && p->parts.empty())  // (its remaining checks; the ones above pass again)
+        return traj_opt(fn, p, sdf, prm, pose, true, targets, ldt, xi, ldx, n_traj, iters, info, ldi, stream);
+    if (p->pose_links.empty()) return bad(KIN_E_UNSUPPORTED, "the plan has no pose links (kin_traj_plan_create)");
+    return traj_parts_run(bad, fn, p, sdf, prm, kTrajPoseMaxChain, pose, targets, ldt, scene_q, lds, xi, ldx, n_traj, iters,
+                          info, ldi, stream);
 }
 
 }  // extern "C"

@@ -819,6 +819,14 @@ function traj_plan!(hm::HIPModel, ::Type{T}, sscc::Kinematics.SweptSphereCollisi
     end
 end
 
+"""The part (0-based; 0 for spheres on one chain) of a `traj_plan!` plan that carries its pose link `i`
+(kin_plan_pose_link_part)."""
+function pose_link_part(plan, i::Integer=0)
+    part = Ref{Int32}(0)
+    check(ccall((:kin_plan_pose_link_part, libkinhip), Cint, (Ptr{Cvoid}, Int32, Ref{Int32}), plan, Int32(i), part))
+    Int(part[])
+end
+
 """`plan_trajectories_pose!(hm, sscc, joints, sdf, Xi, n_wp, link, wp, targets; with_rot, ...)`: `plan_trajectories!`
 with `link` held at `targets` (n_traj, 12; 3x4 column-major per row) at the interior waypoint `wp` (0-based) of
 every trajectory, position only (`with_rot=false`) or position + orientation: the constrained update of
@@ -852,6 +860,48 @@ function plan_trajectories_pose!(hm::HIPModel, sscc::Kinematics.SweptSphereColli
                      Int64, Ptr{Int32}, Ptr{T}, Int64, Ptr{Cvoid}),
                     p, sdf.handle, prm, pose, pointer(targets), stride(targets, 2), pointer(Xi), stride(Xi, 2), n_traj,
                     pointer(iters), pointer(info), n_traj, stream_ptr()))
+    end
+    Xi, iters, info
+end
+
+"""`plan_trajectories_pose_tree!(hm, sscc, joints, sdf, Xi, n_wp, link, wp, targets; scene_q, with_rot, ...)`:
+`plan_trajectories_pose!` for every plan kind through kin_traj_opt_pose_tree_batch: spheres on several chains
+(fridge_demo.jl's `vcat(rarm, larm)`; `link` on either arm) and, with an attached `HIPSDF(scene, scene_joints)`,
+`scene_q` as in `plan_trajectories_scene!` (a door that swings while the robot moves).  The same arrays, keywords and
+results as `plan_trajectories_pose!`; every sphere chain at most 8 steps, at most 4 of them, 20 dof (base included)."""
+function plan_trajectories_pose_tree!(hm::HIPModel, sscc::Kinematics.SweptSphereCollisionChecker,
+                                      joints::Vector{<:Joint}, sdf::HIPSDF, Xi::ROCMatrix{T}, n_wp::Integer, link::Link,
+                                      wp::Integer, targets::ROCMatrix{T};
+                                      scene_q::Union{Nothing,ROCMatrix{T},ROCVector{T}}=nothing, with_rot::Bool=true,
+                                      margin::Real=2e-2, band::Real=3e-2, weight::Real=10.0, feas::Real=1e-3,
+                                      ftol::Real=1e-6, max_step::Real=0.5, max_iters::Integer=200,
+                                      dof_weights::Union{Nothing,Vector{Float64}}=nothing, pose_weight::Real=10.0,
+                                      damp::Real=1e-6, tol_pos::Real=1e-3, tol_rot::Real=1e-3) where {T}
+    sdf.attached == (scene_q !== nothing) ||
+        throw(ArgumentError("scene_q goes with an attached HIPSDF (and an attached HIPSDF needs it)"))
+    N = size(Xi, 1)
+    N % n_wp == 0 || error("size(Xi, 1) must be a multiple of n_wp")
+    scene_q isa ROCMatrix && size(scene_q, 1) != N && error("scene_q must have one row per row of Xi")
+    n_traj = div(N, n_wp)
+    size(targets) == (n_traj, 12) || error("targets must be (n_traj, 12)")
+    p = traj_plan!(hm, T, sscc, joints, link)
+    iters = ROCVector{Int32}(undef, n_traj)
+    info = ROCMatrix{T}(undef, n_traj, 6)
+    lds = scene_q isa ROCMatrix ? stride(scene_q, 2) : 0  # (N, cols) per waypoint, or one vector
+    sq = scene_q === nothing ? Ptr{T}(C_NULL) : pointer(scene_q)
+    dw = dof_weights === nothing ? Float64[] : dof_weights
+    wps, rots = Int32[wp], Int32[with_rot ? 1 : 0]
+    GC.@preserve dw wps rots begin
+        prm = Ref(KinTrajParams(Int32(n_wp), Int32(max_iters), Float64(margin), Float64(band), Float64(weight),
+                                Float64(feas), Float64(ftol), Float64(max_step),
+                                dof_weights === nothing ? Ptr{Float64}(C_NULL) : pointer(dw)))
+        pose = Ref(KinTrajPoseParams(Int32(1), pointer(wps), pointer(rots), Float64(pose_weight), Float64(damp),
+                                     Float64(tol_pos), Float64(tol_rot)))
+        check(ccall((:kin_traj_opt_pose_tree_batch, libkinhip), Cint,
+                    (Ptr{Cvoid}, Ptr{Cvoid}, Ref{KinTrajParams}, Ref{KinTrajPoseParams}, Ptr{T}, Int64, Ptr{T}, Int64,
+                     Ptr{T}, Int64, Int64, Ptr{Int32}, Ptr{T}, Int64, Ptr{Cvoid}),
+                    p, sdf.handle, prm, pose, pointer(targets), stride(targets, 2), sq, lds, pointer(Xi), stride(Xi, 2),
+                    n_traj, pointer(iters), pointer(info), n_traj, stream_ptr()))
     end
     Xi, iters, info
 end

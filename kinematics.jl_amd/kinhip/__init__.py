@@ -25,8 +25,9 @@ from .collision import (  # noqa: F401
 )
 from .planning import (  # noqa: F401
     ConfigurationConstraint, EqConst, IneqConst, Objective, PoseConstraint, construct_problem,
-    collision_aware_ik, create_straight_trajectory, plan_trajectories, plan_trajectory, traj_metric_inverse,
-    traj_opt_batch, traj_opt_pose_batch, traj_opt_scene_batch, traj_opt_tree_batch,
+    collision_aware_ik, create_straight_trajectory, plan_trajectories, plan_trajectories_pose, plan_trajectory,
+    traj_metric_inverse, traj_opt_batch, traj_opt_pose_batch, traj_opt_pose_tree_batch, traj_opt_scene_batch,
+    traj_opt_tree_batch,
 )
 
 FETCH_ARM_JOINTS = [

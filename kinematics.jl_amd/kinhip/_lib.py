@@ -45,6 +45,7 @@ EXPORTS = [
     "kin_traj_opt_batch", "kin_traj_metric_inverse", "kin_plan_chain_bound",
     "kin_traj_plan_create", "kin_traj_opt_pose_batch",
     "kin_traj_opt_tree_batch", "kin_plan_part_count", "kin_plan_part_chain_bound", "kin_traj_opt_scene_batch",
+    "kin_plan_pose_link_part", "kin_traj_opt_pose_tree_batch",
 ]
 
 
@@ -172,6 +173,8 @@ def lib():
         "kin_traj_opt_scene_batch": ([P, P, P, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
         "kin_plan_part_count": ([P, P], C.c_int),
         "kin_plan_part_chain_bound": ([P, I32, P], C.c_int),
+        "kin_plan_pose_link_part": ([P, I32, P], C.c_int),
+        "kin_traj_opt_pose_tree_batch": ([P, P, P, P, P, I64, P, I64, P, I64, I64, P, P, I64, P], C.c_int),
     }
     # KINHIP_LIB may name a tools-only build (tools/ab.py); KINHIP_SKIP_ABI_CHECK=1 is the explicit opt-out
     # for builds of older sources that lack newer entry points

@@ -283,6 +283,16 @@ class TrajPlan(CollisionPlan):
         self.pose_links = list(pose_links)
         super().__init__(sscc, joints, dtype, pose_links=self.pose_links)
 
+    @property
+    def pose_link_parts(self) -> list:
+        """kin_plan_pose_link_part of every pose link: the part (chain program) that carries it."""
+        out = []
+        for k in range(len(self.pose_links)):
+            v = C.c_int32()
+            K.check(K.lib().kin_plan_pose_link_part(self._h, k, C.byref(v)))
+            out.append(v.value)
+        return out
+
 
 class CollisionIKPlan(Plan):
     """kin_coll_ik_plan_create: the IK plan of `link` over `joints` with the tree of the target link and the

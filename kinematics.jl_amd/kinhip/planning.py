@@ -292,14 +292,16 @@ def traj_opt_scene_batch(plan, sdf: AttachedUnionSDF, X: torch.Tensor, n_wp: int
 
 
 def _traj_opt(entry, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step, max_iters, dof_weights, iters,
-              info, stream):
+              info, stream, info_rows=4):
     if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
             or X.shape[1] % int(n_wp) != 0):
         raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
     n_traj = X.shape[1] // int(n_wp)
     dev = X.device
     it = iters if iters is not None else torch.empty(n_traj, dtype=torch.int32, device=dev)
-    nf = info if info is not None else torch.empty((4, n_traj), dtype=plan.dtype, device=dev)
+    nf = info if info is not None else torch.empty((info_rows, n_traj), dtype=plan.dtype, device=dev)
+    if nf.shape != (info_rows, n_traj) or nf.dtype != plan.dtype or it.shape != (n_traj,) or it.dtype != torch.int32:
+        raise ValueError(f"info must be ({info_rows}, {n_traj}) in the plan dtype and iters ({n_traj},) int32")
     dw = None if dof_weights is None else np.ascontiguousarray(np.asarray(dof_weights, np.float64))
     if dw is not None and dw.shape != (plan.n_dof,):
         raise ValueError(f"dof_weights must have {plan.n_dof} entries")
@@ -348,10 +350,64 @@ def traj_opt_pose_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, targets
     return it, nf
 
 
+def traj_opt_pose_tree_batch(plan, sdf: UnionSDF, X: torch.Tensor, n_wp: int, targets: torch.Tensor, wp: int,
+                             scene_q=None, with_rot=True, margin=2e-2, band=3e-2, weight=10.0, feas=1e-3, ftol=1e-6,
+                             max_step=0.5, max_iters=200, dof_weights=None, pose_weight=10.0, damp=1e-6, tol_pos=1e-3,
+                             tol_rot=1e-3, iters=None, info=None, stream=None):
+    """kin_traj_opt_pose_tree_batch: ``traj_opt_pose_batch`` for every ``TrajPlan`` -- spheres on several chains
+    (``plan.n_parts`` > 1, the pose link on any of them: ``plan.pose_link_parts``) and, with an ``AttachedUnionSDF``,
+    `scene_q` as in ``traj_opt_scene_batch`` (a static ``UnionSDF`` takes none).  The same arrays and results as
+    ``traj_opt_pose_batch``; a single-chain plan against a static union runs that call's kernel."""
+    attached = isinstance(sdf, AttachedUnionSDF)
+    if attached != (scene_q is not None):
+        raise ValueError("scene_q goes with an AttachedUnionSDF (and an AttachedUnionSDF needs it)")
+    if (X.dtype != plan.dtype or not X.is_cuda or X.dim() != 2 or X.shape[0] != plan.n_dof or X.stride(1) != 1
+            or X.shape[1] % int(n_wp) != 0):
+        raise ValueError(f"X must be a CUDA {plan.dtype} tensor of shape ({plan.n_dof}, n_traj * n_wp)")
+    n_traj = X.shape[1] // int(n_wp)
+    if (targets.dtype != plan.dtype or not targets.is_cuda or targets.dim() != 2 or targets.shape != (12, n_traj)
+            or (n_traj > 1 and targets.stride(1) != 1)):
+        raise ValueError(f"targets must be a CUDA {plan.dtype} tensor of shape (12, {n_traj})")
+    _same_device(targets, X, "targets")
+    _plan_device(plan, X)
+    _plan_device(sdf, X)
+    sq, lds = None, 0
+    if attached:
+        with torch.cuda.stream(stream or torch.cuda.current_stream(X.device)):   # (the per-trajectory form is expanded)
+            sq, lds = _scene_columns(plan, sdf, scene_q, X, n_traj, int(n_wp))
+    wps, rots = (C.c_int32 * 1)(int(wp)), (C.c_int32 * 1)(1 if with_rot else 0)
+    pp = K.TrajPoseParams(1, C.cast(wps, C.c_void_p), C.cast(rots, C.c_void_p), float(pose_weight), float(damp),
+                          float(tol_pos), float(tol_rot))
+
+    def entry(ph, sh, prm, *rest):
+        return K.lib().kin_traj_opt_pose_tree_batch(ph, sh, prm, C.byref(pp), targets.data_ptr(),
+                                                    max(targets.stride(0), n_traj),
+                                                    sq.data_ptr() if sq is not None and sq.numel() else None, lds, *rest)
+    return _traj_opt(entry, plan, sdf, X, n_wp, margin, band, weight, feas, ftol, max_step, max_iters, dof_weights,
+                     iters, info, stream, info_rows=6)
+
+
 def _pose12(T, dtype, dev):
     """4x4 -> [12, 1] 3x4 column-major on the device."""
     T = np.asarray(T, np.float64).reshape(4, 4)
     return torch.tensor(np.concatenate([T[:3, :3].T.reshape(-1), T[:3, 3]]), dtype=dtype, device=dev).reshape(12, 1)
+
+
+def _seeded_guess(sscc, joints, pose_link, Qs, Qg, n_wp, c, tg, with_rot, dtype, st):
+    """The guess of a pose-constrained plan, X [n_dof, n_traj * n_wp]: waypoint c by the batched IK (kin_ik_dls_batch,
+    64 iterations to 1e-6) from its place on the straight line, then start -> IK answer -> goal."""
+    n_dof, n_traj = Qs.shape
+    i = torch.arange(n_wp, dtype=dtype, device=Qs.device)
+    step = (Qg - Qs) / (n_wp - 1)
+    ikp = sscc.mech.plan(list(joints), out_links=[pose_link], jac_link=pose_link, jac_joints=list(joints), dtype=dtype)
+    Qm = (Qs + step * c).contiguous()
+    ikp.ik_dls(tg, Qm, max_iters=64, tol_pos=1e-6, tol_rot=1e-6, with_rot=1 if with_rot else 0, stream=st)
+    a, b = (i / c)[None, None, :], ((i - c) / (n_wp - 1 - c))[None, None, :]
+    X = torch.where((i <= c)[None, None, :], Qs[:, :, None] + (Qm - Qs)[:, :, None] * a,
+                    Qm[:, :, None] + (Qg - Qm)[:, :, None] * b)
+    X[:, :, c] = Qm
+    X[:, :, n_wp - 1] = Qg
+    return X.reshape(n_dof, n_traj * n_wp).contiguous()
 
 
 def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, Q_start, Q_goal, n_wp: int,
@@ -380,11 +436,37 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     of `dtype` on the device, (n_scene_cols,) for every waypoint of every trajectory, (n_scene_cols, n_traj) per
     trajectory or (n_scene_cols, n_traj * n_wp) per waypoint (``traj_opt_scene_batch``); `check_ends` evaluates
     the starts at the scene state of waypoint 0 and the goals at that of waypoint n_wp - 1.  `pose_link` together
-    with an attached union raises."""
+    with an attached union or with spheres on several chains raises: ``plan_trajectories_pose`` takes those."""
+    return _plan_trajectories(False, sscc, joints, sdf, Q_start, Q_goal, n_wp, margin, band, weight, max_iters, dtype, X0,
+                              stream, feas, ftol, max_step, dof_weights, plan, check_ends, pose_link, pose_wp,
+                              pose_targets, pose_with_rot, pose_weight, pose_tol, scene_q)
+
+
+def plan_trajectories_pose(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, Q_start, Q_goal, n_wp: int,
+                           pose_link, pose_wp, pose_targets, pose_with_rot=True, margin=2e-2, band=3e-2, weight=10.0,
+                           max_iters=200, dtype=torch.float64, X0=None, stream=None, feas=1e-3, ftol=1e-6, max_step=0.5,
+                           dof_weights=None, check_ends=True, pose_weight=10.0, pose_tol=1e-3, scene_q=None, plan=None):
+    """``plan_trajectories`` with `pose_link` held at `pose_targets` at the interior waypoint `pose_wp`, for every
+    plan kind: with the checker's spheres on one chain and a static union it is ``plan_trajectories(pose_link=...)``
+    itself (bit-equal); with spheres on several chains (`pose_link` on any of them) and / or an ``AttachedUnionSDF``
+    with its `scene_q` it takes kin_traj_opt_pose_tree_batch (``traj_opt_pose_tree_batch``).  The arguments, the
+    seeding of the guess (the constrained waypoint by the batched IK, then two straight lines), `check_ends` and the
+    results (info: 6 rows) are those of ``plan_trajectories``; `plan`: a ``TrajPlan`` of (sscc, joints, [pose_link],
+    dtype) to reuse."""
+    return _plan_trajectories(True, sscc, joints, sdf, Q_start, Q_goal, n_wp, margin, band, weight, max_iters, dtype, X0,
+                              stream, feas, ftol, max_step, dof_weights, plan, check_ends, pose_link, pose_wp,
+                              pose_targets, pose_with_rot, pose_weight, pose_tol, scene_q)
+
+
+def _plan_trajectories(pose_any, sscc, joints, sdf, Q_start, Q_goal, n_wp, margin, band, weight, max_iters, dtype, X0,
+                       stream, feas, ftol, max_step, dof_weights, plan, check_ends, pose_link, pose_wp, pose_targets,
+                       pose_with_rot, pose_weight, pose_tol, scene_q):
+    """``plan_trajectories`` (pose_any False: a pose link takes one sphere chain and a static union) and
+    ``plan_trajectories_pose``."""
     n_wp = int(n_wp)
     dev = _device()
     attached = isinstance(sdf, AttachedUnionSDF)
-    if attached and pose_link is not None:
+    if attached and pose_link is not None and not pose_any:
         raise ValueError("pose_link with an AttachedUnionSDF: pose constraints against a moving scene are not "
                          "supported (kin_traj_opt_scene_batch takes none)")
     if attached != (scene_q is not None):
@@ -396,7 +478,7 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
     else:
         if pose_wp is None or pose_targets is None or not 1 <= int(pose_wp) <= n_wp - 2:
             raise ValueError(f"pose_link needs pose_targets and an interior pose_wp (1..{n_wp - 2})")
-        if (plan if plan is not None else sscc.plan(list(joints), dtype=dtype)).n_parts > 1:
+        if not pose_any and (plan if plan is not None else sscc.plan(list(joints), dtype=dtype)).n_parts > 1:
             raise ValueError("pose_link: the checker's spheres hang off several chains (kin_traj_opt_pose_batch "
                              "takes one sphere chain)")
         plan = plan if plan is not None else sscc.traj_plan(list(joints), [pose_link], dtype=dtype)
@@ -463,19 +545,14 @@ def plan_trajectories(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, 
             X[:, :, n_wp - 1] = Qg
             X = X.reshape(n_dof, n_traj * n_wp).contiguous()
         else:
-            # the constrained waypoint by IK from its place on the straight line, then start -> IK answer -> goal
-            c = int(pose_wp)
-            ikp = sscc.mech.plan(list(joints), out_links=[pose_link], jac_link=pose_link, jac_joints=list(joints),
-                                 dtype=dtype)
-            Qm = (Qs + step * c).contiguous()
-            ikp.ik_dls(tg, Qm, max_iters=64, tol_pos=1e-6, tol_rot=1e-6, with_rot=1 if pose_with_rot else 0, stream=st)
-            a, b = (i / c)[None, None, :], ((i - c) / (n_wp - 1 - c))[None, None, :]
-            X = torch.where((i <= c)[None, None, :], Qs[:, :, None] + (Qm - Qs)[:, :, None] * a,
-                            Qm[:, :, None] + (Qg - Qm)[:, :, None] * b)
-            X[:, :, c] = Qm
-            X[:, :, n_wp - 1] = Qg
-            X = X.reshape(n_dof, n_traj * n_wp).contiguous()
-        if attached:
+            X = _seeded_guess(sscc, joints, pose_link, Qs, Qg, n_wp, int(pose_wp), tg, pose_with_rot, dtype, st)
+        if pose_link is not None and (attached or plan.n_parts > 1):
+            it, nf = traj_opt_pose_tree_batch(plan, sdf, X, n_wp, tg, int(pose_wp), scene_q=scene_q,
+                                              with_rot=pose_with_rot, margin=margin, band=band, weight=weight, feas=feas,
+                                              ftol=ftol, max_step=max_step, max_iters=max_iters,
+                                              dof_weights=dof_weights, pose_weight=pose_weight, tol_pos=pose_tol,
+                                              tol_rot=pose_tol, stream=st)
+        elif attached:
             it, nf = traj_opt_scene_batch(plan, sdf, X, n_wp, scene_q, margin=margin, band=band, weight=weight, feas=feas,
                                           ftol=ftol, max_step=max_step, max_iters=max_iters, dof_weights=dof_weights,
                                           stream=st)
@@ -503,7 +580,8 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
     the axis-angle residual to 1e-3; status ``:SUCCESS`` when it ended feasible within `maxiter`, else
     ``:MAXEVAL_REACHED``; ``ftol_abs`` is not used).  "GPU" only: `sdf` may be an ``AttachedUnionSDF`` with
     `scene_q` its scene columns, (n_scene_cols,) or (n_scene_cols, n_wp) -- one scene state per waypoint
-    (kin_traj_opt_scene_batch; no partial constraint then)."""
+    (kin_traj_opt_scene_batch); a ``PoseConstraint`` with spheres on several chains or with an attached union goes
+    through ``plan_trajectories_pose``."""
     from scipy.optimize import minimize
     from .collision import compute_coll_dists
 
@@ -521,8 +599,10 @@ def plan_trajectory(sscc: SweptSphereCollisionChecker, joints, sdf: UnionSDF, q_
                       pose_with_rot=pc.with_rots[0])
         if scene_q is not None:
             kw["scene_q"] = torch.as_tensor(scene_q, dtype=torch.float64).to(_device())
-        X, it, _ = plan_trajectories(sscc, joints, sdf, np.asarray(q_start, np.float64), np.asarray(q_goal, np.float64),
-                                     n_wp, margin=margin, max_iters=maxiter, dtype=torch.float64, **kw)
+        # (a pose constraint: every plan kind; on one sphere chain with a static union it is plan_trajectories itself)
+        X, it, _ = (plan_trajectories_pose if pcs else plan_trajectories)(
+            sscc, joints, sdf, np.asarray(q_start, np.float64), np.asarray(q_goal, np.float64), n_wp, margin=margin,
+            max_iters=maxiter, dtype=torch.float64, **kw)
         return X.cpu().numpy(), (":SUCCESS" if int(it[0]) <= maxiter else ":MAXEVAL_REACHED")
     if solver in ("NLOPT", "IPOPT"):
         raise ValueError(f"solver :{solver} needs a library that is not installed; use 'SLSQP_BOUNDED' "

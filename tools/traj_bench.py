@@ -8,6 +8,7 @@ the host, one GPU constraint evaluation per iterate) looped over the same 32 pro
     python tools/traj_bench.py [--reps 5] [--no-slsqp] [--out profiles/traj_bench.json]
     python tools/traj_bench.py --scene pr2 [--out profiles/traj_bench_pr2.json]
     python tools/traj_bench.py --scene pr2-door [--out profiles/traj_bench_scene.json]
+    python tools/traj_bench.py --pose [--out profiles/traj_bench_pose_tree.json]
 
 --scene pr2: the reference's fridge_demo.jl shape -- the PR2 (tests/golden/pr2_two_arms.urdf) with both arms and
 the planar base (17 columns), kinhip.PR2_ARM_SPHERES on two chains (kin_traj_opt_tree_batch), the static fridge
@@ -23,6 +24,14 @@ AttachedUnionSDF(fridge, [door_joint]): (a) "uniform", one scene state for the l
 interleaved (static, uniform, swing, static, ...), "static": kin_traj_opt_tree_batch on the static snapshot, and
 ratio_to_static = the uniform leg's median over that one's.  Feasibility is re-evaluated with kin_coll_batch_scene
 at every waypoint's own scene state.
+
+--pose: the pr2 leg's robot, goals and fridge with the left tool frame held at waypoint 5 (6 rows) through
+kinhip.plan_trajectories_pose (kin_traj_opt_pose_tree_batch, k_traj_pose_tree; the IK seeding of the guess is inside the
+timed call): "static" against the static union and "swing" with the door closing from 2.0 to 1.2 over the waypoints.
+The target of problem t is the tool frame's pose at waypoint 5 of its straight line, moved by (-0.05, 0, 0.10) and
+turned by 0.3 rad about z.  good_of_32: |r_p|, |r_rot| < 1e-3 and clearance >= margin - feas.  Beside them the only
+path there was before: kinhip.plan_trajectory (SLSQP on the host) with the PoseConstraint, looped over the 32 static
+problems (it cannot take the moving door).
 
 Timing: a host clock around calls that end in a device synchronise, after a warm-up call per shape; the median of
 --reps repeats and their min / max.  Iterations per second counts, per trajectory, the iterations the kernel ran
@@ -157,6 +166,63 @@ def door_legs(a, res, joints, sscc, sdf, q_start, G, cp64):
                 print(json.dumps(row), flush=True)
 
 
+def pose_legs(a, res, m, joints, sscc, sdf, q_start, G, cp64):
+    """--pose: the left tool frame at waypoint 5, static union and swinging door (k_traj_pose_tree), then the SLSQP loop."""
+    link, c = m.find_link("l_gripper_tool_frame"), 5
+    fridge = kinhip.parse_urdf(os.path.join(ROOT, "tests", "golden", "fridge.urdf"), with_base=True)
+    att = kinhip.AttachedUnionSDF(fridge, [fridge.find_joint("door_joint")])
+    qs = torch.tensor(q_start, dtype=torch.float64, device="cuda")[:, None]
+    Qc = (qs + (G - qs) * (c / (N_WP - 1))).contiguous()
+    T = kinhip.get_transform_batch(m, [link], joints, Qc).double().reshape(12, 32)
+    cz, sz = np.cos(0.3), np.sin(0.3)
+    Rz = torch.tensor([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]], dtype=torch.float64, device="cuda")
+    Rm = Rz @ T[:9].T.reshape(32, 3, 3).transpose(1, 2)                     # (3x4 column-major -> R, turned)
+    tg32 = torch.cat([Rm.transpose(1, 2).reshape(32, 9).T, T[9:12] + torch.tensor([[-0.05], [0.0], [0.10]], device="cuda")])
+    for dtype in (torch.float32, torch.float64):
+        tp = sscc.traj_plan(joints, [link], dtype=dtype)
+        for n_traj in (32, 1024, 32768):
+            Qg = G.repeat(1, n_traj // 32).to(dtype).contiguous()
+            tg = tg32.repeat(1, n_traj // 32).to(dtype).contiguous()
+            swing = torch.tensor([2.0, 1.2, 0.0, 0.0], dtype=dtype, device="cuda")[:, None].repeat(1, n_traj * N_WP)
+            swing[0] = torch.linspace(2.0, 1.2, N_WP, dtype=dtype, device="cuda").repeat(n_traj)
+            legs = (("static", sdf, None), ("swing", att, swing))
+            out = {}
+
+            def call_of(mode, s, sq):
+                def call():
+                    out[mode] = kinhip.plan_trajectories_pose(sscc, joints, s, q_start, Qg, N_WP, link, c, tg,
+                                                              margin=MARGIN, feas=FEAS, max_iters=MAX_ITERS, dtype=dtype,
+                                                              plan=tp, check_ends=False, scene_q=sq)
+                return call
+            times = timed_interleaved([call_of(*leg) for leg in legs], a.reps)
+            for (mode, s, sq), (med, lo, hi) in zip(legs, times):
+                X, it, info = out[mode]
+                ran = torch.clamp(it, max=MAX_ITERS).sum().item()
+                d = interior_clearance(cp64, s, X, n_traj, None if sq is None else sq.double())
+                ok = (d[:32] >= MARGIN - FEAS - (1e-6 if dtype == torch.float32 else 0.0)) \
+                    & (info[4, :32] < 1e-3) & (info[5, :32] < 1e-3)
+                row = {"mode": mode, "dtype": str(dtype).split(".")[-1], "n_traj": n_traj, "seconds_median": med,
+                       "seconds_min": lo, "seconds_max": hi, "traj_per_s": n_traj / med, "iters_per_s": ran / med,
+                       "mean_iters": ran / n_traj, "good_of_32": int(ok.sum()),
+                       "done_of_32": int((it[:32] <= MAX_ITERS).sum())}
+                res["gpu"].append(row)
+                print(json.dumps(row), flush=True)
+    if not a.no_slsqp:
+        Gh, th = G.cpu().numpy(), tg32.cpu().numpy()
+        t0 = time.perf_counter()
+        ok = 0
+        for t in range(32):
+            T4 = np.eye(4)
+            T4[:3, :3], T4[:3, 3] = th[:9, t].reshape(3, 3).T, th[9:12, t]
+            pc = kinhip.PoseConstraint(c + 1, len(q_start), link, T4, True, m, joints)
+            _, status = kinhip.plan_trajectory(sscc, joints, sdf, q_start, Gh[:, t], N_WP, margin=MARGIN, ftol_abs=1e-5,
+                                               partial_consts=[pc])
+            ok += int(status == ":SUCCESS")
+        dt = time.perf_counter() - t0
+        res["slsqp"] = {"mode": "static", "n_traj": 32, "seconds": dt, "traj_per_s": 32 / dt, "success_of_32": ok}
+        print(json.dumps(res["slsqp"]), flush=True)
+
+
 def timed(fn, reps):
     fn()  # warm-up: code objects, the metric table, allocator
     torch.cuda.synchronize()
@@ -175,7 +241,10 @@ def main():
     ap.add_argument("--no-slsqp", action="store_true")
     ap.add_argument("--out", default="")
     ap.add_argument("--scene", choices=("fetch", "pr2", "pr2-door"), default="fetch")
+    ap.add_argument("--pose", action="store_true", help="the left tool frame held at waypoint 5 (implies the pr2 scene)")
     a = ap.parse_args()
+    if a.pose:
+        a.scene = "pr2"
     if not torch.cuda.is_available():
         sys.exit("traj_bench.py needs a GPU")
     if a.scene in ("pr2", "pr2-door"):
@@ -196,8 +265,9 @@ def main():
     res = {"scene": name, "n_wp": N_WP, "max_iters": MAX_ITERS, "parts": cp64.n_parts,
            "straight_infeasible_of_32": int((d0 < MARGIN - FEAS).sum()), "gpu": []}
     print(json.dumps({k: v for k, v in res.items() if k != "gpu"}), flush=True)
-    if a.scene == "pr2-door":
-        door_legs(a, res, joints, sscc, sdf, q_start, G, cp64)
+    if a.scene == "pr2-door" or a.pose:
+        (pose_legs(a, res, m, joints, sscc, sdf, q_start, G, cp64) if a.pose else
+         door_legs(a, res, joints, sscc, sdf, q_start, G, cp64))
         if a.out:
             with open(a.out, "w") as f:
                 json.dump(res, f, indent=1)
